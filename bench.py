@@ -10,15 +10,24 @@ One step = one pass of the whole hot path over one batch of synthetic frames.  B
 start in HOST memory and reach HBM through frame_loader.FrameLoader's staging thread and copy stream, up to four batches ahead of
 the step that consumes them (the metric starts at the H2D copy of the raw frame), so every step after the first
 finds its inputs resident when it starts; --input resident keeps the raw clouds and images in HBM (rounds 1-4's headline; it runs
-as a short second leg and is reported beside `value` either way).  The path: voxelise + project (raw 100k-point clouds), KNN for the 4 fusion sites, ResNet-18 image
+under --full as a short second leg and is reported beside `value` either way).  The path: voxelise + project (raw 100k-point clouds), KNN for the 4 fusion sites, ResNet-18 image
 stream + FPN, LiDAR-BEV stream with 4 continuous-fusion adds, heads/decode, LossTotal,
 backward, gradient all-reduce (RCCL, N>1) and the fused Adam step.  Workload = BASELINE.json
 configs[1] ("cfg2"): KITTI-scale grid 32x704x800, 100k points, 1242x375 RGB, ResNet-18, K=3,
 batch 2 per GPU, bf16 (fp32 accumulate / fp32 master weights).  Weak scaling: per-GPU batch fixed.
 
-Prints ONE JSON line on rank 0 (see README / task contract), including
-  roofline     -- the dominant kernel class, timed live with HIP events on the launch stream
+Prints ONE JSON line on rank 0 (see README / task contract).  A plain run sets up, warms up, times the --steps steps, writes
+--dump-outputs if asked and prints the line: nothing else runs on the GPU or the host.  --full adds, after the timed steps,
+  other leg   -- the input mode that is not timed as `value` (from host / resident), a short second leg (N=1)
+  batch sweep -- resident-input rates at the other batch sizes of BASELINE.json's metric (N=1)
+  roofline    -- the dominant kernel class, timed live with HIP events on the launch stream, + per-kernel / per-class tables
   cpu_baseline -- this repo's CPU restatement (oracle/, kind "port") on a bounded sample, rank 0, N=1 only.
+Their fields are null in a plain run; each can still be switched off under --full by its --no-* flag.
+
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR
+writes what the last timed step computed as DIR/<name>.npy (see dump_outputs).  The frames are seeded and the last timed step
+starts from the seeded weights and optimiser state (SeededState), so two builds run with the same arguments can be compared
+output for output.
 """
 import argparse
 import copy
@@ -351,9 +360,20 @@ def host_core_counts():
     return (len(phys) or None), os.cpu_count()
 
 
+def cpu_allotment():
+    """CPUs this process may run on: its affinity mask, capped by OMP_NUM_THREADS where the environment sets it (a shared host can
+    hand a job fewer CPUs than os.cpu_count() reports, and threads beyond them only slow each other down)."""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    omp = os.environ.get("OMP_NUM_THREADS", "").strip()
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return max(n, 1)
+
+
 def cpu_baseline(cfg, pool_seed):
     """The CPU restatement (oracle/, kind 'port': the reference has no camera stream / KNN / fusion code to run, SURVEY.md
-    F1) on a bounded sample of the same workload: ONE cfg2 frame through the whole step on all host cores (<= 32 threads) --
+    F1) on a bounded sample of the same workload: ONE cfg2 frame through the whole step on the CPUs allotted to the process
+    (cpu_allotment(), <= 32 threads) --
     geometry (C), the brute-force KNN of the four sites (C, OpenMP over pixel rows: timed on its own, it is not what the
     baseline should be decided by), the fused model forward of oracle/model_ref.py (camera ResNet-18 + FPN, LiDAR stream,
     bilinear gather + per-neighbour MLP at each site), the reference's LossTotal restated in oracle/loss_ref.py, backward,
@@ -364,7 +384,7 @@ def cpu_baseline(cfg, pool_seed):
     det = pkg("detfill")
     D = pkg("data_import_carla")
     c = copy.deepcopy(cfg)
-    threads = min(os.cpu_count() or 1, 32)        # more threads than this oversubscribes oneDNN on these shapes
+    threads = min(cpu_allotment(), 32)            # more threads than this oversubscribes oneDNN on these shapes
     torch.set_num_threads(threads)
     lim6 = (c["lidar_x_min"], c["lidar_x_max"], c["lidar_y_min"], c["lidar_y_max"], c["lidar_z_min"], c["lidar_z_max"])
     pts = det.synthetic_points(c["max_num_pc"], lim6, pool_seed)
@@ -430,6 +450,66 @@ def cpu_baseline(cfg, pool_seed):
                       "(C, OpenMP) %.2fs + fused forward (ResNet-18 camera stream, LiDAR stream, gather + per-neighbour MLP at 4 sites) %.2fs + "
                       "LossTotal + backward + Adam %.2fs; one-thread figure = LiDAR stream fwd + LossTotal + bwd on a 176x192 crop scaled by the "
                       "area ratio (%.1fs)" % (threads, t_geo, t_knn, t_fwd, t_bwd, t_one)}
+
+
+DUMP_SAMPLE = 1 << 20          # elements written per arena by --dump-outputs (4 MB as float32; five arenas stay far below 64 MB)
+DUMP_SEED = 0
+
+
+def dump_outputs(trainer, outdir, sample=DUMP_SAMPLE, seed=DUMP_SEED):
+    """--dump-outputs: what the last timed step hands its caller, as <outdir>/<name>.npy (float32).  A train step returns nothing:
+    its results are the loss it computed and the state it leaves -- the parameter arena after the Adam step, that step's gradient
+    arena, Adam's two moment arenas and the BatchNorm buffers.  An arena longer than `sample` elements is written as a fixed sample
+    of `sample` of them: indices drawn once from numpy's generator seeded with `seed`, sorted, the same for every run and every
+    arena of that length.  Returns the names written."""
+    os.makedirs(outdir, exist_ok=True)
+    out = {"loss": trainer.loss_value.detach().float().reshape(1).cpu().numpy()}
+    arenas = (("params", trainer.model.flat_params), ("grads", trainer.model.flat_grads), ("adam_m", trainer.optimizer.m),
+              ("adam_v", trainer.optimizer.v), ("buffers", trainer.model._bufflat))
+    picks = {}
+    for name, t in arenas:
+        t = t.detach().reshape(-1)
+        n = t.numel()
+        if n > sample:
+            if n not in picks:
+                idx = np.sort(np.random.default_rng(seed).choice(n, sample, replace=False))
+                picks[n] = torch.from_numpy(idx).to(t.device)
+            t = t.index_select(0, picks[n])
+        out[name] = t.float().cpu().numpy()
+    for name, a in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return sorted(out)
+
+
+class SeededState(object):
+    """The state a train step reads and updates besides its frames, as the seeded set-up left it: the parameter arena, Adam's
+    moments and step count, the BatchNorm buffers (and, on the fp8 path, the delayed activation scales, which start at zero).
+    restore() puts it back in place (same addresses: captured graphs stay valid) with copies on the current stream."""
+
+    def __init__(self, trainer):
+        self.trainer = trainer
+        self.saved = [(t, t.detach().clone()) for t in (trainer.model.flat_params, trainer.optimizer.m, trainer.optimizer.v,
+                                                          trainer.model._bufflat)]
+        self.step_count = trainer.optimizer.step_count
+
+    def restore(self):
+        with torch.no_grad():
+            for t, s in self.saved:
+                t.copy_(s)
+            K = self.trainer.model._backend
+            if K is not None and getattr(K, "amax", None) is not None:
+                K.amax.zero_()
+        self.trainer.optimizer.step_count = self.step_count
+
+
+def extra_legs(args, ws):
+    """The legs that run after the timed steps: none in a plain run (its line needs only the timed steps); under --full each of
+    them unless its --no-* flag is given.  The other input mode, the batch sweep and the CPU baseline run on one rank only."""
+    full = bool(args.full)
+    return {"other_leg": full and ws == 1 and not args.no_other_leg,
+            "batch_sweep": full and ws == 1 and not args.no_batch_sweep,
+            "roofline": full and not args.no_roofline,
+            "cpu_baseline": full and ws == 1 and not args.no_cpu_baseline}
 
 
 def rank_envs(n, port, base=None):
@@ -500,23 +580,32 @@ def main():
     ap.add_argument("--input", default="host", choices=["host", "resident"],
                     help="where the timed steps' frames start: host (default) = host memory -> pinned staging on FrameLoader's background "
                     "thread -> H2D on a copy stream one batch ahead (SURVEY.md 8(d): the metric starts at the H2D copy of the raw frame; "
-                    "VERDICT round 4 item 2); resident = raw clouds and images already in HBM.  The other mode runs as a short second leg "
-                    "and is reported beside `value`")
+                    "VERDICT round 4 item 2); resident = raw clouds and images already in HBM.  Under --full the other mode runs as a short "
+                    "second leg and is reported beside `value`")
     ap.add_argument("--from-host", action="store_true", help="same as --input host (kept from earlier rounds)")
     ap.add_argument("--no-from-host", action="store_true", help="--input resident without the second (from-host) leg")
-    ap.add_argument("--no-other-leg", action="store_true", help="skip the second leg (the input mode that is not timed as `value`)")
+    ap.add_argument("--no-other-leg", action="store_true", help="skip the second leg (the input mode that is not timed as `value`; --full only)")
     ap.add_argument("--loss-sampling", default="compat", help="compat = host target assignment on numpy's generator exactly like the reference's "
                     "loss.py:74-127 (default, the mode pinned to the reference); device = assignment + loss in one launch (csrc/loss.hip)")
     ap.add_argument("--loader-workers", type=int, default=0, help="DataLoader worker processes behind FrameLoader in the from-host loop "
                     "(0 = the staging thread reads and collates itself)")
     ap.add_argument("--chain", action="store_true", help="run the residual stages' 3x3 layers as chain launches (dcf_conv3x3_chain: one launch per "
                     "stage; needs the GPU to itself; level on time with the per-layer launches, DESIGN.md section 9)")
-    ap.add_argument("--no-batch-sweep", action="store_true", help="skip the short resident-input legs at the other batch sizes of BASELINE.json's metric (1 / 2 / 4 / 8)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--no-batch-sweep", action="store_true", help="skip the short resident-input legs at the other batch sizes of BASELINE.json's metric "
+                    "(1 / 2 / 4 / 8; --full only).  Also keeps the frame pool at 4 frames instead of 8")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline (--full only)")
+    ap.add_argument("--no-roofline", action="store_true", help="skip the instrumented roofline pass (--full only)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the other input mode, the batch sweep, the roofline "
+                    "pass and the CPU baseline (a plain run only times its steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy "
+                    "(loss; fixed, seeded samples of the parameter, gradient, Adam-moment and BatchNorm arenas; float32)")
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
     env_ws = os.environ.get("WORLD_SIZE")
     if env_ws is None and args.gpus > 1:
         # `python bench.py --gpus N` typed without a launcher: this process becomes the launcher (it has not touched the GPU and
@@ -552,6 +641,9 @@ def main():
     np.random.seed(1234 + rank)
     trainer = train.Train(cfg)
     pkg("detfill").fill_state_dict(trainer.model)        # deterministic random-init weights (no checkpoints offline)
+    seeded = SeededState(trainer)
+    legs = extra_legs(args, ws)
+    # (the pool's size decides which frames the timed steps see: it depends on the flags alone, not on whether the sweep runs)
     pool = FramePool(cfg, n_frames=max(2 * args.batch, 4 if (ws > 1 or args.no_batch_sweep) else 8), n_points=args.points, seed0=100 * rank)
 
     def barrier():
@@ -589,6 +681,11 @@ def main():
     t0 = time.perf_counter()
     marks[0].record()
     for s in range(args.steps):
+        if s == args.steps - 1:
+            # The last timed step starts from the seeded state, not from what the steps before it left: float atomics in the
+            # backward leave last-bit differences between runs, and training amplifies them step after step.  So what the last
+            # step computes (final_loss, --dump-outputs) depends on the arguments alone.  A few copies, enqueued once.
+            seeded.restore()
         if loader is not None:
             trainer.one_step_raw(pool.geometry, next(loader))
         else:
@@ -608,11 +705,13 @@ def main():
     loss = float(trainer.loss_value.item())
     frames_main = args.batch * ws * args.steps
     log("timed region done: %.3f s" % dt)
+    if args.dump_outputs and rank == 0:                 # before any later leg moves the trainer on
+        log("outputs written: %s" % ", ".join(dump_outputs(trainer, args.dump_outputs)))
 
     roof, breakdown, classes, cpu, from_host, resident = None, None, None, None, None, None
     if loader is not None:
         loader.close()                                  # stops the staging thread
-    if not args.no_other_leg and ws == 1:
+    if legs["other_leg"]:
         # the OTHER input mode of the same step, as a short second leg reported beside `value`
         n_o = min(args.steps, 20)
         if args.from_host:
@@ -640,7 +739,7 @@ def main():
             from_host = {"value": round(args.batch * n_o / dt_o, 3), "unit": "frames/s", "ms_per_step": round(dt_o / n_o * 1e3, 3), "steps": n_o,
                          "note": "same step fed from host memory through FrameLoader (PCIe-inclusive)"}
     sweep = None
-    if ws == 1 and not args.no_batch_sweep:
+    if legs["batch_sweep"]:
         # BASELINE.json's metric names batch 1 / 2 / 4 / 8: the other batch sizes of the same workload on the same trainer, resident
         # input, 10 timed steps each behind 4 untimed ones (batch 1 replays captured graphs under --graphs auto: they are captured there)
         sweep = {}
@@ -658,12 +757,12 @@ def main():
             sweep[str(b)] = {"frames_per_s": round(b * 10 / dt_b, 2), "ms_per_step": round(dt_b / 10 * 1e3, 3)}
         sweep[str(args.batch)] = {"frames_per_s": resident["value"] if resident else (round(frames_main / dt, 2) if not args.from_host else None),
                                   "ms_per_step": resident["ms_per_step"] if resident else (round(dt / args.steps * 1e3, 3) if not args.from_host else None)}
-    if not args.no_roofline:
+    if legs["roofline"]:
         # every rank runs the instrumented steps (they contain the gradient all-reduce); rank 0 reports its own
         roof, breakdown, classes = roofline_leg(trainer, pool, args.batch, 2)
     if ws > 1:
         dist.barrier()
-    if rank == 0 and ws == 1 and not args.no_cpu_baseline:
+    if rank == 0 and legs["cpu_baseline"]:
         cpu = cpu_baseline(cfg, 1234)
     if rank == 0:
         frames = args.batch * ws * args.steps

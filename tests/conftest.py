@@ -50,13 +50,14 @@ def _start_dp_children(config):
             procs.append(("n2_r%d" % rank, subprocess.Popen([sys.executable, child, "rccl2", str(rank), port3, outdir], stdout=log,
                                                             stderr=subprocess.STDOUT, cwd=ROOT)))
     # ... and bench.py itself exactly as the driver types it -- `python bench.py --gpus 2 ...`, NO launcher and none of its variables
-    # in the environment: bench.py has to start its two ranks itself (both on this one GPU, gloo instead of RCCL)
+    # in the environment: bench.py has to start its two ranks itself (both on this one GPU, gloo instead of RCCL).  --full: the
+    # test reads the roofline the ranks report, which a plain run no longer measures
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["DCF_DIST_BACKEND"] = "gloo"
     out = open(os.path.join(outdir, "bench_launch.out"), "w")
     log = open(os.path.join(outdir, "bench_launch.log"), "w")
     procs.append(("bench_launch", subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                                                    "--no-cpu-baseline"], stdout=out, stderr=log, cwd=ROOT, env=env)))
+                                                    "--full", "--no-cpu-baseline"], stdout=out, stderr=log, cwd=ROOT, env=env)))
     # ... and the repeatability stress runs of tests/test_gpu_stress.py (they start their own sibling process before touching the GPU)
     if not os.environ.get("DCF_NO_STRESS_CHILDREN"):
         for mode in ("stream", "sibling"):

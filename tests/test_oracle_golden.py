@@ -79,7 +79,15 @@ def test_anchors_and_decode():
     a = model_ref.anchors(cfg).numpy()
     assert np.array_equal(a.view(np.uint32), z["anchors_carla"].view(np.uint32))
     box = model_ref.decode(torch.from_numpy(z["reg"]), torch.from_numpy(z["anchors_tiny"])).numpy()
-    assert np.array_equal(box, z["box"])
+    want = z["box"]
+    # centre / height channels are +, * and sqrt only (correctly rounded on every CPU): bit for bit.  Size (exp) and yaw
+    # (atan2(sin, cos)) channels go through math routines whose last bits depend on the CPU torch runs on (up to 2 units in
+    # the last place apart between the hosts this suite runs on): within 4 units in the last place there.
+    exact = [0, 1, 2, 7, 8, 9]
+    assert np.array_equal(box[:, exact], want[:, exact])
+    libm = [3, 4, 5, 6, 10, 11, 12, 13]
+    err = np.abs(box[:, libm].astype(np.float64) - want[:, libm])
+    assert (err <= 4 * np.spacing(np.abs(want[:, libm]))).all(), "max deviation %g" % err.max()
 
 
 @pytest.mark.parametrize("mode", ["eval", "train"])
