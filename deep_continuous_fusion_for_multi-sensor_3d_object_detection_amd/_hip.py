@@ -109,6 +109,9 @@ SIGNATURES = {
     "dcf_loss_sample_fwd_bwd": (c_int, [P, c_i64, P, c_i64, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float,
                                         c_int, c_int, c_int, c_int, ctypes.c_uint64, c_float, c_int, P, P, c_i64, P, c_i64, P, P, P, P]),
     "dcf_adam_step": (c_int, [P, P, P, P, c_i64, c_float, c_float, c_float, c_float, c_int, c_float, P]),
+    "dcf_grad_stats": (c_int, [P, c_i64, P, P]),
+    "dcf_amp_update": (c_int, [P, c_float, c_int, ctypes.c_double, ctypes.c_double, c_int, c_float, c_float, c_float, c_float, P]),
+    "dcf_adam_step_guarded": (c_int, [P, P, P, P, c_i64, c_float, c_float, c_float, P, P]),
 }
 
 
@@ -154,6 +157,17 @@ class KnnSite(ctypes.Structure):
     """struct dcf_knn_site of include/dcf_hip.h."""
     _fields_ = [("h", ctypes.c_int32), ("w", ctypes.c_int32), ("stride", ctypes.c_int32), ("fine", ctypes.c_int32), ("idx_out", c_void_p),
                 ("ws", c_void_p), ("ws_stride_bytes", ctypes.c_size_t)]
+
+
+AMP_PARTS = 1024             # DCF_AMP_PARTS
+
+
+class AmpState(ctypes.Structure):
+    """struct dcf_amp_state of include/dcf_hip.h (the guarded optimiser step's device state)."""
+    _fields_ = [("scale_in", c_float), ("scale_next", c_float), ("growth_tracker", ctypes.c_int32), ("found_inf", ctypes.c_int32),
+                ("applied_steps", c_i64), ("skipped_steps", c_i64), ("grad_norm", c_float), ("clip_coef", c_float),
+                ("gscale", c_float), ("lr_over_bc1", c_float), ("inv_sqrt_bc2", c_float), ("pad_", ctypes.c_int32 * 3),
+                ("part_sum", c_float * AMP_PARTS), ("part_flag", ctypes.c_int32 * AMP_PARTS)]
 
 
 class DcfError(RuntimeError):

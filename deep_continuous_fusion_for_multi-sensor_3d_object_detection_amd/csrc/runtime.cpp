@@ -27,7 +27,7 @@ extern "C" const char *dcf_last_error(void) { return g_err; }
 // mismatch would have bound them at load and failed with "undefined symbol" instead.  The major moves now, and the policy is
 // written down ("Versions"): removing or changing an exported symbol = new major; adding = new minor.
 // 201: + dcf_relu_mask_rowscale_bwd
-extern "C" int dcf_version(void) { return 201; }
+extern "C" int dcf_version(void) { return 202; }
 
 // ------------------------------------------------------------------ tuning options (dcf_common.h)
 std::atomic<int> g_dcf_opt_epoch{0};

@@ -288,6 +288,43 @@ def adam_step(params, grads, m, v, lr, beta1, beta2, eps, step, gscale=1.0):
     H.call("dcf_adam_step", params, grads, m, v, params.numel(), lr, beta1, beta2, eps, step, gscale, H.stream_ptr())
 
 
+# ------------------------------------------------------------------ guarded optimiser step (csrc/amp.hip)
+class AmpState(object):
+    """struct dcf_amp_state in one fp32 device tensor (`raw`), with 0-d views of its fields.  The views alias the device
+    memory: reading one with .item() synchronises, using one in a torch expression does not."""
+
+    WORDS = ctypes.sizeof(H.AmpState) // 4
+
+    def __init__(self, device, scale=1.0):
+        self.raw = torch.zeros(self.WORDS, dtype=torch.float32, device=device)
+        f = {name: getattr(H.AmpState, name).offset // 4 for name, _ in H.AmpState._fields_}
+        r = self.raw
+        self.scale_in, self.scale_next = r[f["scale_in"]], r[f["scale_next"]]
+        self.growth_tracker = r[f["growth_tracker"]:f["growth_tracker"] + 1].view(torch.int32)[0]
+        self.found_inf = r[f["found_inf"]:f["found_inf"] + 1].view(torch.int32)[0]
+        self.applied_steps = r[f["applied_steps"]:f["applied_steps"] + 2].view(torch.int64)[0]
+        self.skipped_steps = r[f["skipped_steps"]:f["skipped_steps"] + 2].view(torch.int64)[0]
+        self.grad_norm, self.clip_coef = r[f["grad_norm"]], r[f["clip_coef"]]
+        self.gscale, self.lr_over_bc1, self.inv_sqrt_bc2 = r[f["gscale"]], r[f["lr_over_bc1"]], r[f["inv_sqrt_bc2"]]
+        self.header = r[:f["part_sum"]]              # everything but the partials workspace: what a checkpoint carries
+        self.scale_in.fill_(scale)
+        self.scale_next.fill_(scale)
+
+
+def grad_stats(grads, state):
+    H.call("dcf_grad_stats", grads, grads.numel(), state.raw, H.stream_ptr())
+
+
+def amp_update(state, gscale_host, dynamic, growth_factor, backoff_factor, growth_interval, max_norm, lr, beta1, beta2):
+    """max_norm None = no clipping."""
+    H.call("dcf_amp_update", state.raw, gscale_host, 1 if dynamic else 0, growth_factor, backoff_factor, growth_interval,
+           0.0 if max_norm is None else max_norm, lr, beta1, beta2, H.stream_ptr())
+
+
+def adam_step_guarded(params, grads, m, v, beta1, beta2, eps, state):
+    H.call("dcf_adam_step_guarded", params, grads, m, v, params.numel(), beta1, beta2, eps, state.raw, H.stream_ptr())
+
+
 # ------------------------------------------------------------------ geometry
 class GridSpec(object):
     """Grid constants of CarlaDataset.__init__ (data_import_carla.py:35-43) and the filter

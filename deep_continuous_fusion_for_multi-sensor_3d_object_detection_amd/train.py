@@ -16,22 +16,100 @@ from ._hip import torch_dtype as H_torch_dtype
 from .model import ObjectDetection_DCF
 
 
-class FlatAdam(object):
-    """Adam(lr, betas=(beta1, 0.999), eps=1e-8) of train.py:28 on the flat parameter arena."""
+def parse_guard_config(cfg):
+    """The guarded optimiser step's keys (config_carla.yaml), validated; None = none of them set (the plain Adam step).
+      loss_scale                      none | a positive number (static scale; 1 = the non-finite skip alone) | dynamic
+      loss_scale_init                 first dynamic scale (GradScaler's 65536)
+      loss_scale_growth_factor / loss_scale_backoff_factor / loss_scale_growth_interval    GradScaler's 2.0 / 0.5 / 2000
+      grad_clip_norm                  null | maximum global L2 norm of the averaged, unscaled gradient
+    Bad values raise ValueError."""
+    import math
 
-    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8):
+    def number(key, default):
+        v = cfg.get(key, default)
+        if isinstance(v, bool):
+            raise ValueError("%s must be a number (got %r)" % (key, v))
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            raise ValueError("%s must be a number (got %r)" % (key, v))
+        if not math.isfinite(f):
+            raise ValueError("%s must be finite (got %r)" % (key, v))
+        return f
+
+    ls = cfg.get("loss_scale", "none")
+    if ls is None or (isinstance(ls, str) and ls.strip().lower() == "none"):
+        mode, scale = None, 1.0
+    elif isinstance(ls, str) and ls.strip().lower() == "dynamic":
+        mode, scale = "dynamic", number("loss_scale_init", 65536.0)
+        if scale <= 0:
+            raise ValueError("loss_scale_init must be positive (got %r)" % (cfg.get("loss_scale_init"),))
+    else:
+        scale = number("loss_scale", None)
+        if scale <= 0:
+            raise ValueError("loss_scale must be none, dynamic or a positive number (got %r)" % (ls,))
+        mode = "static"
+    growth = number("loss_scale_growth_factor", 2.0)
+    backoff = number("loss_scale_backoff_factor", 0.5)
+    if growth <= 1.0:
+        raise ValueError("loss_scale_growth_factor must be > 1 (got %r)" % (growth,))
+    if not 0.0 < backoff < 1.0:
+        raise ValueError("loss_scale_backoff_factor must be in (0, 1) (got %r)" % (backoff,))
+    gi = cfg.get("loss_scale_growth_interval", 2000)
+    if isinstance(gi, bool) or not isinstance(gi, int) or gi < 1:
+        raise ValueError("loss_scale_growth_interval must be a positive integer (got %r)" % (gi,))
+    clip = cfg.get("grad_clip_norm", None)
+    if clip is not None:
+        clip = number("grad_clip_norm", None)
+        if clip <= 0:
+            raise ValueError("grad_clip_norm must be positive or null (got %r)" % (cfg.get("grad_clip_norm"),))
+    if mode is None and clip is None:
+        return None
+    return {"mode": mode, "scale": scale, "growth_factor": growth, "backoff_factor": backoff, "growth_interval": gi,
+            "max_norm": clip}
+
+
+class FlatAdam(object):
+    """Adam(lr, betas=(beta1, 0.999), eps=1e-8) of train.py:28 on the flat parameter arena.
+    guard (parse_guard_config): the guarded step of csrc/amp.hip -- loss scale, non-finite skip and clipping decided on the
+    device; the bias-correction count is then the device's applied-step count (step_count reads it: a synchronisation)."""
+
+    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, guard=None):
         self.model, self.lr, self.betas, self.eps = model, lr, betas, eps
-        self.step_count = 0
+        self._step_count = 0
         self.m = torch.zeros_like(model.flat_params)
         self.v = torch.zeros_like(model.flat_params)
+        self.guard = guard
+        self.amp = ops.AmpState(model.flat_params.device, guard["scale"]) if guard is not None else None
+
+    @property
+    def step_count(self):
+        if self.amp is not None:
+            return int(self.amp.applied_steps.item())
+        return self._step_count
+
+    @step_count.setter
+    def step_count(self, value):
+        if self.amp is not None:
+            self.amp.applied_steps.fill_(int(value))
+        else:
+            self._step_count = int(value)
 
     def zero_grad(self):
         pass  # the backward pass overwrites the gradient arena
 
     def step(self, gscale=1.0):
-        self.step_count += 1
+        if self.amp is not None:
+            g = self.guard
+            ops.grad_stats(self.model.flat_grads, self.amp)
+            ops.amp_update(self.amp, gscale, g["mode"] == "dynamic", g["growth_factor"], g["backoff_factor"], g["growth_interval"],
+                           g["max_norm"], self.lr, self.betas[0], self.betas[1])
+            ops.adam_step_guarded(self.model.flat_params, self.model.flat_grads, self.m, self.v, self.betas[0], self.betas[1],
+                                  self.eps, self.amp)
+            return
+        self._step_count += 1
         ops.adam_step(self.model.flat_params, self.model.flat_grads, self.m, self.v, self.lr, self.betas[0], self.betas[1],
-                      self.eps, self.step_count, gscale)
+                      self.eps, self._step_count, gscale)
 
     def state_dict(self):
         return {"step": self.step_count, "m": self.m, "v": self.v}
@@ -81,7 +159,9 @@ class Train(nn.Module):
         self.loss_total = LossTotal(config)
         self.model = ObjectDetection_DCF(config).cuda()
         self.loss_value = None
-        self.optimizer = FlatAdam(self.model, config["learning_rate"], (config["beta1"], 0.999))
+        # guarded optimiser step (loss_scale / grad_clip_norm; None = the plain Adam step, the default)
+        self.guard = parse_guard_config(config)
+        self.optimizer = FlatAdam(self.model, config["learning_rate"], (config["beta1"], 0.999), guard=self.guard)
         self.sync_replicas()
         self._side = None
         self.static_geometry = bool(config.get("static_geometry", True))
@@ -109,7 +189,9 @@ class Train(nn.Module):
         call it again after loading weights or a checkpoint on rank 0 only)."""
         for t in (self.model.flat_params, self.model._bufflat, self.optimizer.m, self.optimizer.v):
             broadcast_from_rank0(t)
-        if world() > 1:                          # Adam's bias correction depends on it
+        if self.optimizer.amp is not None:       # loss scale, growth tracker and step counters (the applied count included)
+            broadcast_from_rank0(self.optimizer.amp.raw)
+        elif world() > 1:                        # Adam's bias correction depends on it
             sc = torch.tensor([self.optimizer.step_count], dtype=torch.int64)
             if dist.get_backend() != "gloo":
                 sc = sc.to(self.model.flat_params.device)
@@ -289,7 +371,12 @@ class Train(nn.Module):
         if overlap:
             self.model._backend.bucket_hook = self._bucket_ready
         try:
-            self.loss_value.backward()
+            if self.optimizer.amp is not None:
+                # seeded with the device's loss scale: a one-element multiply, no read on the host (_FusedLoss.backward scales its
+                # gradient maps by the incoming gradient; under hip_graphs they reach the captured backward through its static buffer)
+                (self.loss_value * self.optimizer.amp.scale_next).backward()
+            else:
+                self.loss_value.backward()
         finally:
             if overlap:
                 self.model._backend.bucket_hook = None
@@ -320,12 +407,27 @@ class Train(nn.Module):
         x_lidar, geom = self.geometry_async(frame_geometry, batch["points"], crts=batch.get("crt"), wait_event=batch.event)
         self.one_step(x_lidar, batch["image"], batch["bboxes"], batch["num_bboxes"], geom=geom)
 
+    # ------------------------------------------------------------------ guarded step: device-side read-outs (no synchronisation)
+    def loss_scale(self):
+        """The scale the next backward is seeded with (device tensor, a copy); None without loss_scale / grad_clip_norm."""
+        return None if self.optimizer.amp is None else self.optimizer.amp.scale_next.clone()
+
+    def grad_norm(self):
+        """Global L2 norm of the last step's averaged, unscaled gradient (device tensor, a copy; before clipping)."""
+        return None if self.optimizer.amp is None else self.optimizer.amp.grad_norm.clone()
+
+    def skipped_steps(self):
+        """Steps skipped for a non-finite gradient so far (device int64 tensor, a copy)."""
+        return None if self.optimizer.amp is None else self.optimizer.amp.skipped_steps.clone()
+
     # ------------------------------------------------------------------ checkpoint / resume (SURVEY.md 8(f) N4)
     def save_checkpoint(self, path, epoch=0):
         """Model state_dict (the reference's key names, train.py:79) plus what the reference never saved:
         optimiser moments / step count and the epoch, so that training can really resume."""
         sd = {k: v.detach().clone().contiguous().cpu() for k, v in self.model.state_dict().items()}
         opt = {"step": self.optimizer.step_count, "m": self.optimizer.m.cpu(), "v": self.optimizer.v.cpu()}
+        if self.optimizer.amp is not None:         # the guard state (scale, growth tracker, counters), without the partials workspace
+            opt["amp"] = self.optimizer.amp.header.cpu()
         torch.save({"model": sd, "optimizer": opt, "epoch": int(epoch), "loss_calls": int(getattr(self.loss_total, "calls", 0))}, path)
 
     def load_checkpoint(self, path):
@@ -335,7 +437,10 @@ class Train(nn.Module):
             return 0
         self.model.load_state_dict(ck["model"])
         self.optimizer.load_state_dict({k: (v.to(self.model.flat_params.device) if torch.is_tensor(v) else v)
-                                        for k, v in ck["optimizer"].items()})
+                                        for k, v in ck["optimizer"].items() if k != "amp"})
+        amp = ck["optimizer"].get("amp")
+        if self.optimizer.amp is not None and amp is not None:
+            self.optimizer.amp.header.copy_(amp)    # a checkpoint without it keeps the configured initial scale
         if hasattr(self.loss_total, "calls"):       # device sampling: a resumed run continues the draw sequence instead of replaying it
             self.loss_total.calls = int(ck.get("loss_calls", self.optimizer.step_count))
         return int(ck.get("epoch", 0))

@@ -387,6 +387,43 @@ int dcf_cast(int dtype_src, const void *src, int dtype_dst, void *dst, int64_t n
 int dcf_adam_step(float *params, const float *grads, float *m, float *v, int64_t n, float lr, float beta1,
                   float beta2, float eps, int step, float gscale, dcf_stream_t stream);
 
+/* (version 202) The guarded Adam step of train.py:28,36 (csrc/amp.hip): loss scaling -- a static scale, or the dynamic schedule
+ * of torch.amp.GradScaler -- an exact skip of a step whose gradient holds a NaN or an inf, and global-norm clipping, decided on the
+ * device (the host never waits).  One block of device memory holds the state (8-byte aligned; zero it, then set scale_next):
+ *   scale_next      the scale the NEXT backward is seeded with (loss * scale_next); written by dcf_amp_update
+ *   scale_in        the scale the current backward used: latched from scale_next by dcf_grad_stats, read by dcf_amp_update
+ *   growth_tracker  clean steps since the last change of a dynamic scale (torch._amp_update_scale_)
+ *   found_inf       1 = the last dcf_amp_update skipped its step
+ *   applied_steps / skipped_steps   Adam's bias-correction count t = applied_steps
+ *   grad_norm       L2 norm of the gradient Adam sees (sqrt(sum g^2) * |gscale_host| / scale_in)
+ *   clip_coef       min(1, max_norm / (grad_norm + 1e-6)); exactly 1 when not clipped
+ *   gscale, lr_over_bc1, inv_sqrt_bc2   the step's Adam scalars (gscale_host / scale_in * clip_coef, and dcf_adam_step's host
+ *                   expressions for t, in double, rounded to float)
+ *   part_sum / part_flag   workspace: dcf_grad_stats' per-workgroup partial sums of g^2 and non-finite flags
+ * A step is three launches on one stream, after the gradient arena is final (all-reduced):
+ *   dcf_grad_stats(grads, n, state)  reads the arena once (4n bytes, fixed grid of DCF_AMP_PARTS workgroups: bit-reproducible)
+ *   dcf_amp_update(state, ...)       one workgroup: found_inf = any NaN / +-inf, or a non-finite norm while clipping
+ *                                     (max_norm > 0; <= 0 = no clipping); dynamic != 0: GradScaler's rule (back off on found_inf,
+ *                                     grow after growth_interval clean steps); static: the scale stays
+ *   dcf_adam_step_guarded(...)       dcf_adam_step's arithmetic with the state's scalars; stores nothing when found_inf is set
+ * grads must be 16-byte aligned. */
+#define DCF_AMP_PARTS 1024
+typedef struct dcf_amp_state {
+    float scale_in, scale_next;
+    int32_t growth_tracker, found_inf;
+    int64_t applied_steps, skipped_steps;
+    float grad_norm, clip_coef;
+    float gscale, lr_over_bc1, inv_sqrt_bc2;
+    int32_t pad_[3];
+    float part_sum[DCF_AMP_PARTS];
+    int32_t part_flag[DCF_AMP_PARTS];
+} dcf_amp_state;
+int dcf_grad_stats(const float *grads, int64_t n, dcf_amp_state *state, dcf_stream_t stream);
+int dcf_amp_update(dcf_amp_state *state, float gscale_host, int dynamic, double growth_factor, double backoff_factor,
+                   int growth_interval, float max_norm, float lr, float beta1, float beta2, dcf_stream_t stream);
+int dcf_adam_step_guarded(float *params, const float *grads, float *m, float *v, int64_t n, float beta1, float beta2, float eps,
+                          const dcf_amp_state *state, dcf_stream_t stream);
+
 /* dcf_fusion_gather_bwd driven by dcf_fusion_invert's pairs (Cb in {64,128,192,256}): same sums, no idx -> point -> row
  * dependency chain.  The map's pairs are [*e_begin, *e_end) = start[g*(n_max+1)], start[g*(n_max+1)+n_max];
  * max_entries = K*h*w sizes the grid.
