@@ -108,6 +108,20 @@ SIGNATURES = {
     "dcf_loss_sample_rand": (ctypes.c_uint32, [ctypes.c_uint64, c_int, c_int, c_int, c_int]),
     "dcf_loss_sample_fwd_bwd": (c_int, [P, c_i64, P, c_i64, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float,
                                         c_int, c_int, c_int, c_int, ctypes.c_uint64, c_float, c_int, P, P, c_i64, P, c_i64, P, P, P, P]),
+    # deterministic mode (csrc/fusion_det.hip, the DET instantiations of csrc/loss.hip)
+    "dcf_inv_sort_segments": (c_int, [P, c_int, P, P, P]),
+    "dcf_cam_invert_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dcf_cam_invert": (c_int, [P, c_i64, P, c_int, c_int, c_int, c_int, P, P, P, P, P]),
+    "dcf_point_sample_bwd_det": (c_int, [c_int, P, c_i64, c_int, c_int, c_int, P, c_i64, P, P, P, c_int, P]),
+    "dcf_fusion_gather_bwd_det_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dcf_fusion_gather_bwd_det": (c_int, [c_int, P, c_i64, P, c_i64, P, c_int, P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float,
+                                          P, P, c_int, P, P, P, P, P, c_int, P]),
+    "dcf_rowscale_bias_bwd_det_workspace_bytes": (c_size_t, [c_int]),
+    "dcf_rowscale_bias_bwd_det": (c_int, [c_int, P, P, P, P, P, c_i64, c_int, P, P]),
+    "dcf_rows_fold": (c_int, [P, c_int, c_int, P, P]),
+    "dcf_loss_fwd_bwd_det": (c_int, [P, c_i64, P, c_i64, P, P, P, c_int, c_int, c_float, c_int, P, P, c_i64, P, c_i64, P, P]),
+    "dcf_loss_sample_fwd_bwd_det": (c_int, [P, c_i64, P, c_i64, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float,
+                                            c_int, c_int, c_int, c_int, ctypes.c_uint64, c_float, c_int, P, P, c_i64, P, c_i64, P, P, P, P, P]),
     "dcf_adam_step": (c_int, [P, P, P, P, c_i64, c_float, c_float, c_float, c_float, c_int, c_float, P]),
     "dcf_grad_stats": (c_int, [P, c_i64, P, P]),
     "dcf_amp_update": (c_int, [P, c_float, c_int, ctypes.c_double, ctypes.c_double, c_int, c_float, c_float, c_float, c_float, P]),

@@ -518,10 +518,26 @@ class HipBackend(object):
     _gp_pool = None
     _group = os.environ.get("DCF_WGRAD_GROUP", "1") != "0"
     # one-writer-per-point fusion backward (dcf_fusion_gather_bwd_pts: no zero-fill, no atomics on dP, no cast): correct, but a
-    # point that thousands of pixels chose is then one wave's serial work -- measured 1.07 vs 0.30 ms per step at cfg2, so off
+    # point that thousands of pixels chose is then one wave's serial work -- measured 1.07 vs 0.30 ms per step at cfg2, so off.
+    # (`deterministic: true` has its own balanced one-writer kernel, dcf_fusion_gather_bwd_det: see `deterministic` below.)
     _fusion_pts = os.environ.get("DCF_FUSION_PTS", "0") == "1"
     # "0" = the fp32 accumulator + cast form of the inverse-map backward again (A/B runs)
     _fusion_direct = os.environ.get("DCF_FUSION_DIRECT", "1") != "0"
+
+    # deterministic: true (set by the model from its config, never from the environment here): the fusion backward, the point-sample
+    # backward and fc2's bias gradient take the fixed-order kernels of csrc/fusion_det.hip.  A call those kernels cannot serve is
+    # an error, never a quiet return to the atomic ones.
+    deterministic = False
+    _det_ws = None
+
+    def _det_workspace(self, key, make):
+        """Persistent (fixed address: captured graphs keep it) workspace of a fixed-order kernel."""
+        if self._det_ws is None:
+            self._det_ws = {}
+        ws = self._det_ws.get(key)
+        if ws is None:
+            ws = self._det_ws[key] = make()
+        return ws
 
     def conv_wgrad(self, L, x, gy, defer=True):
         """defer=False: gy (or x) is modified in place later in the backward (e.g. masked by a ReLU) -- launch now."""
@@ -611,7 +627,13 @@ class HipBackend(object):
             ops.point_sample_fwd(self.dtype, fmap[b], uv[b], cnt[b:b + 1], n_max, out=fp[b])
         return fp
 
-    def point_sample_bwd(self, gfp, uv, cnt, n_max, fmap_shape, gF):
+    def point_sample_bwd(self, gfp, uv, cnt, n_max, fmap_shape, gF, cam_inv=None):
+        if self.deterministic:
+            if cam_inv is None or gF is not None or not (uv.is_contiguous() and gfp.is_contiguous()):
+                raise H.DcfError("deterministic: the point-sample backward needs the camera-pixel map of the step (model.fusion_inverse), "
+                                 "contiguous inputs and no gradient to add to")
+            gF = torch.empty(fmap_shape, dtype=torch.float32, device=self.dev)      # every row is stored by the kernel
+            return ops.point_sample_bwd_det(self.dtype, gfp, uv, cam_inv, gF)
         if gF is None:
             gF = torch.zeros(fmap_shape, dtype=torch.float32, device=self.dev)
         if uv.is_contiguous() and cnt.is_contiguous() and gfp.is_contiguous() and n_max > 0 and gfp.shape[1] == n_max:
@@ -634,6 +656,17 @@ class HipBackend(object):
         """inv: inverse KNN maps of the step (ops.fusion_invert, map = site*B + frame) -> the point-sorted backward;
         else the pixel-run one."""
         use_inv = inv is not None and P.shape[2] % 64 == 0 and 64 <= P.shape[2] <= 256
+        if self.deterministic:
+            if not (use_inv and P.is_contiguous() and xyz.is_contiguous() and ghsum.is_contiguous() and P.shape[0] <= 64):
+                raise H.DcfError("deterministic: the fusion backward needs the sorted inverse KNN maps, 64/128/192/256 channels, contiguous "
+                                 "tensors and at most 64 frames")
+            khw = tuple(idx.shape[-3:])
+            key = ("fgd", khw[0] * khw[1] * khw[2], P.shape[2], P.shape[0])
+            ws = self._det_workspace(key, lambda: ops.fusion_bwd_det_workspace(self.dev, *key[1:]))
+            gP = torch.empty(P.shape, dtype=P.dtype, device=self.dev)              # every row is stored by the kernel
+            ops.fusion_gather_bwd_det(self.dtype, P, xyz, inv, inv_nmax or P.shape[1], site * P.shape[0], khw, stride, aff,
+                                      self._pbase + 4 * w1d_off, self._pbase + 4 * b1_off, ghsum, gP, self._gbase + 4 * w1d_off, self._gbase + 4 * b1_off, ws)
+            return gP
         if use_inv and self._fusion_pts:
             # one writer per point row: the gradient comes out whole, in the compute dtype (no zero-fill, no atomics on it, no cast)
             gP = torch.empty(P.shape, dtype=P.dtype, device=self.dev)
@@ -699,7 +732,14 @@ class HipBackend(object):
 
     def relu_mask_rowscale_bwd(self, gy, y, cnt, b2_off):
         """At a fusion site: the masked gradient for the stage's last block (a new tensor) + fc2's bias gradient, one pass."""
+        if self.deterministic:
+            C = gy.shape[-1]
+            return ops.rowscale_bias_bwd_det(self.dtype, gy, cnt, self._gbase + 4 * b2_off, self._det_workspace(("rbd", C), lambda: ops.rowscale_bias_det_workspace(self.dev, C)), y=y)
         return ops.relu_mask_rowscale_bwd(self.dtype, gy, y, cnt, self._gbase + 4 * b2_off)
 
     def rowscale_bias_bwd(self, gy, cnt, b2_off):
+        if self.deterministic:
+            C = gy.shape[-1]
+            ops.rowscale_bias_bwd_det(self.dtype, gy, cnt, self._gbase + 4 * b2_off, self._det_workspace(("rbd", C), lambda: ops.rowscale_bias_det_workspace(self.dev, C)))
+            return
         ops.rowscale_bias_bwd(self.dtype, gy, cnt, self._gbase + 4 * b2_off)

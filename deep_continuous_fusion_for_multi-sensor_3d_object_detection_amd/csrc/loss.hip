@@ -31,18 +31,41 @@ __device__ __forceinline__ float block_sum16(float v, float *red)
     return t;
 }
 
+// encoded regression target of component j of a box against the anchor at a cell (an = anchor parameters of the cell, HW apart)
+__device__ __forceinline__ float reg_target(const float *bx, const float *an, int j, int HW)
+{
+    if (j < 2) {
+        const float l = an[3 * HW], w = an[4 * HW];
+        return (bx[j] - an[j * HW]) / sqrtf(l * l + w * w);
+    }
+    if (j == 2) return (bx[2] - an[2 * HW]) / an[5 * HW];
+    if (j < 6) return logf(bx[j] / an[j * HW]);
+    const float d = bx[6] - an[6 * HW];
+    return atan2f(sinf(d), cosf(d));
+}
+__device__ __forceinline__ float sl1_grad(float d) { return fabsf(d) < 1.f ? d : (d > 0.f ? 1.f : -1.f); }
+
+// DET (deterministic: true): a cell can occur several times in a sample's lists (overlapping positive windows,
+// negatives drawn with replacement), and three or more float atomics onto one address do not commute.  There the FIRST entry of a
+// cell adds the terms of all entries of that cell in list order and stores the sum once; the sample's loss value goes to its own
+// slot of loss_rows (k_loss_rows_fold adds the slots in sample order).  The lists hold a few hundred entries: the scans are cheap.
+
 // ints  = [B x {off_int, npos, nneg, nrow, off_float, nbox}] then per sample: pos cells, neg cells, reg cells, box of each reg cell
 // floats = per sample: weight of each reg cell, then nbox x 7 box parameters
 // (1024 threads: with the reference's 'last' reduction ONE workgroup does all the work, and its entries are chains of dependent
 // loads -- list item -> cell -> scores -> atomics; at 256 threads the launch took 40 us between forward and backward)
+template <bool DET>
 __global__ void __launch_bounds__(1024) k_loss_fwd_bwd(const float *cls, int64_t cls_bs, const float *reg, int64_t reg_bs, const float *anc,
                                                       const int64_t *ints, const float *floats, int B, int HW, float gain, int reduction,
-                                                      float *loss, float *gcls, int64_t gcls_bs, float *greg, int64_t greg_bs)
+                                                      float *loss, float *gcls, int64_t gcls_bs, float *greg, int64_t greg_bs, float *loss_rows)
 {
     __shared__ float red[16];
     const int b = blockIdx.x;
     // reduction 0 = 'last' (reference behaviour: only the last sample counts), 1 = 'sum', 2 = 'mean'
-    if (reduction == 0 && b != B - 1) return;
+    if (reduction == 0 && b != B - 1) {
+        if (DET && threadIdx.x == 0) loss_rows[b] = 0.f;
+        return;
+    }
     const float wsample = reduction == 2 ? 1.f / (float)B : 1.f;
     const int64_t *pl = ints + 6 * b;
     const int o = (int)pl[0], npos = (int)pl[1], nneg = (int)pl[2], nrow = (int)pl[3], of = (int)pl[4];
@@ -51,6 +74,22 @@ __global__ void __launch_bounds__(1024) k_loss_fwd_bwd(const float *cls, int64_t
     const float *c = cls + b * cls_bs, *r = reg + b * reg_bs;
     float *gc = gcls + b * gcls_bs, *gr = greg + b * greg_bs;
     float acc = 0.f;
+    const int *lcell = nullptr, *lrow = nullptr;      // DET: the cells of the two lists staged in LDS (the scans below read them often)
+    if constexpr (DET) {
+        // DCF-DET-BEGIN
+        constexpr int MAXL = 2048;
+        __shared__ int s_cell[MAXL], s_row[MAXL];
+        if (npos + nneg <= MAXL) {
+            for (int i = threadIdx.x; i < npos + nneg; i += blockDim.x) s_cell[i] = (int)(i < npos ? pos[i] : neg[i - npos]);
+            lcell = s_cell;
+        }
+        if (nrow <= MAXL) {
+            for (int i = threadIdx.x; i < nrow; i += blockDim.x) s_row[i] = (int)rows[i];
+            lrow = s_row;
+        }
+        __syncthreads();
+        // DCF-DET-END
+    }
     // ---- classification: entry e = (anchor a, list item)
     const int ncls = 2 * (npos + nneg);
     for (int e = threadIdx.x; e < ncls; e += blockDim.x) {
@@ -65,8 +104,29 @@ __global__ void __launch_bounds__(1024) k_loss_fwd_bwd(const float *cls, int64_t
         const float p0 = e0 / (e0 + e1), p1 = e1 / (e0 + e1);
         acc += (lse - (is_pos ? s1 : s0)) * inv;
         const float g = inv * wsample;
-        atomicAdd(gc + (int64_t)(2 * a) * HW + cell, (p0 - (is_pos ? 0.f : 1.f)) * g);
-        atomicAdd(gc + (int64_t)(2 * a + 1) * HW + cell, (p1 - (is_pos ? 1.f : 0.f)) * g);
+        if constexpr (DET) {
+            // DCF-DET-BEGIN
+            const int nl = npos + nneg;
+            auto cell_at = [&](int j) { return lcell ? lcell[j] : (int)(j < npos ? pos[j] : neg[j - npos]); };
+            bool first = true;
+            for (int j = 0; j < it && first; ++j) first = cell_at(j) != cell;
+            if (first) {
+                float g0 = 0.f, g1 = 0.f;
+                for (int j = it; j < nl; ++j) {
+                    if (cell_at(j) != cell) continue;
+                    const bool jp = j < npos;
+                    const float gj = (1.f / (float)(jp ? npos : nneg)) * wsample;
+                    g0 += (p0 - (jp ? 0.f : 1.f)) * gj;
+                    g1 += (p1 - (jp ? 1.f : 0.f)) * gj;
+                }
+                gc[(int64_t)(2 * a) * HW + cell] += g0;
+                gc[(int64_t)(2 * a + 1) * HW + cell] += g1;
+            }
+            // DCF-DET-END
+        } else {
+            atomicAdd(gc + (int64_t)(2 * a) * HW + cell, (p0 - (is_pos ? 0.f : 1.f)) * g);
+            atomicAdd(gc + (int64_t)(2 * a + 1) * HW + cell, (p1 - (is_pos ? 1.f : 0.f)) * g);
+        }
     }
     // ---- regression: entry e = (row, anchor a, component j)
     float accr = 0.f;
@@ -76,25 +136,44 @@ __global__ void __launch_bounds__(1024) k_loss_fwd_bwd(const float *cls, int64_t
         const int cell = (int)rows[row];
         const float *bx = boxes + (int64_t)rbox[row] * 7;
         const float *an = anc + (int64_t)a * 7 * HW + cell;     // an[j * HW]
-        float t;
-        if (j < 2) {
-            const float l = an[3 * HW], w = an[4 * HW];
-            t = (bx[j] - an[j * HW]) / sqrtf(l * l + w * w);
-        } else if (j == 2) {
-            t = (bx[2] - an[2 * HW]) / an[5 * HW];
-        } else if (j < 6) {
-            t = logf(bx[j] / an[j * HW]);
-        } else {
-            const float d = bx[6] - an[6 * HW];
-            t = atan2f(sinf(d), cosf(d));
-        }
+        const float t = reg_target(bx, an, j, HW);
         const float d = r[(int64_t)q * HW + cell] - t;
         const float ad = fabsf(d);
         accr += (ad < 1.f ? 0.5f * d * d : ad - 0.5f) * wrow[row];
-        atomicAdd(gr + (int64_t)q * HW + cell, (ad < 1.f ? d : (d > 0.f ? 1.f : -1.f)) * wrow[row] * gain * wsample);
+        if constexpr (DET) {
+            // DCF-DET-BEGIN
+            auto row_cell = [&](int r2) { return lrow ? lrow[r2] : (int)rows[r2]; };
+            bool first = true;
+            for (int r2 = 0; r2 < row && first; ++r2) first = row_cell(r2) != cell;
+            if (first) {
+                float gs = 0.f;
+                for (int r2 = row; r2 < nrow; ++r2) {
+                    if (row_cell(r2) != cell) continue;
+                    const float d2 = r[(int64_t)q * HW + cell] - reg_target(boxes + (int64_t)rbox[r2] * 7, an, j, HW);
+                    gs += sl1_grad(d2) * wrow[r2] * gain * wsample;
+                }
+                gr[(int64_t)q * HW + cell] += gs;
+            }
+            // DCF-DET-END
+        } else {
+            atomicAdd(gr + (int64_t)q * HW + cell, (ad < 1.f ? d : (d > 0.f ? 1.f : -1.f)) * wrow[row] * gain * wsample);
+        }
     }
     const float tot = block_sum16(acc + gain * accr, red);
-    if (threadIdx.x == 0) atomicAdd(loss, tot * wsample);
+    if constexpr (DET) {
+        if (threadIdx.x == 0) loss_rows[b] = tot * wsample;
+    } else {
+        if (threadIdx.x == 0) atomicAdd(loss, tot * wsample);
+    }
+}
+
+// *loss += rows[0] + rows[1] + ... in sample order
+__global__ void k_loss_rows_fold(const float *rows, int n, float *loss)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    float tot = 0.f;
+    for (int i = 0; i < n; ++i) tot += rows[i];
+    *loss += tot;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -127,13 +206,14 @@ struct LossSampleArgs {
     const float *cls, *reg, *anc, *boxes;
     const int32_t *nbox;
     int64_t cls_bs, reg_bs, gcls_bs, greg_bs;
-    float *loss, *gcls, *greg;
+    float *loss, *gcls, *greg, *loss_rows;
     int32_t *pos_out, *neg_out, *counts_out;
     uint64_t seed;
     int max_box, box_stride, B, H, W, span, regress_type, pos_cap, neg_count, reduction;
     float xs, xo, ys, yo, rs, gain;
 };
 
+template <bool DET>
 __global__ void __launch_bounds__(256) k_loss_sample_fwd_bwd(LossSampleArgs a)
 {
     __shared__ float red[4];
@@ -213,7 +293,10 @@ __global__ void __launch_bounds__(256) k_loss_sample_fwd_bwd(LossSampleArgs a)
         for (int i = tid; i < a.neg_count; i += blockDim.x) a.neg_out[(int64_t)b * a.neg_count + i] = negs[i];
     if (a.counts_out && tid == 0) { a.counts_out[2 * b] = npos; a.counts_out[2 * b + 1] = np; }
     // reduction 0 = 'last' (reference behaviour: only the last sample counts), 1 = 'sum', 2 = 'mean'
-    if (a.reduction == 0 && b != a.B - 1) return;
+    if (a.reduction == 0 && b != a.B - 1) {
+        if (DET && tid == 0) a.loss_rows[b] = 0.f;
+        return;
+    }
     const float wsample = a.reduction == 2 ? 1.f / (float)a.B : 1.f;
     const float *c = a.cls + b * a.cls_bs, *r = a.reg + b * a.reg_bs;
     float *gc = a.gcls + b * a.gcls_bs, *gr = a.greg + b * a.greg_bs;
@@ -232,8 +315,29 @@ __global__ void __launch_bounds__(256) k_loss_sample_fwd_bwd(LossSampleArgs a)
         const float p0 = e0 / (e0 + e1), p1 = e1 / (e0 + e1);
         acc += (lse - (is_pos ? s1 : s0)) * inv;
         const float g = inv * wsample;
-        atomicAdd(gc + (int64_t)(2 * an) * HW + cell, (p0 - (is_pos ? 0.f : 1.f)) * g);
-        atomicAdd(gc + (int64_t)(2 * an + 1) * HW + cell, (p1 - (is_pos ? 1.f : 0.f)) * g);
+        if constexpr (DET) {
+            // DCF-DET-BEGIN
+            const int nl = npos + nneg;
+            auto cell_at = [&](int j) { return j < npos ? sel[j] : negs[j - npos]; };
+            bool first = true;
+            for (int j = 0; j < it && first; ++j) first = cell_at(j) != cell;
+            if (first) {
+                float g0 = 0.f, g1 = 0.f;
+                for (int j = it; j < nl; ++j) {
+                    if (cell_at(j) != cell) continue;
+                    const bool jp = j < npos;
+                    const float gj = (1.f / (float)(jp ? npos : nneg)) * wsample;
+                    g0 += (p0 - (jp ? 0.f : 1.f)) * gj;
+                    g1 += (p1 - (jp ? 1.f : 0.f)) * gj;
+                }
+                gc[(int64_t)(2 * an) * HW + cell] += g0;
+                gc[(int64_t)(2 * an + 1) * HW + cell] += g1;
+            }
+            // DCF-DET-END
+        } else {
+            atomicAdd(gc + (int64_t)(2 * an) * HW + cell, (p0 - (is_pos ? 0.f : 1.f)) * g);
+            atomicAdd(gc + (int64_t)(2 * an + 1) * HW + cell, (p1 - (is_pos ? 1.f : 0.f)) * g);
+        }
     }
     // ---- regression rows: every window entry (regress_type 0) or the centre cell only; a box's rows share its weight 1 / (rows * 14)
     float accr = 0.f;
@@ -249,25 +353,38 @@ __global__ void __launch_bounds__(256) k_loss_sample_fwd_bwd(LossSampleArgs a)
         const int an_ = q / 7, j = q - an_ * 7;
         const float *bk = bx + (int64_t)k * a.box_stride;
         const float *an = a.anc + (int64_t)an_ * 7 * HW + cell;
-        float t;
-        if (j < 2) {
-            const float l = an[3 * HW], w = an[4 * HW];
-            t = (bk[j] - an[j * HW]) / sqrtf(l * l + w * w);
-        } else if (j == 2) {
-            t = (bk[2] - an[2 * HW]) / an[5 * HW];
-        } else if (j < 6) {
-            t = logf(bk[j] / an[j * HW]);
-        } else {
-            const float d = bk[6] - an[6 * HW];
-            t = atan2f(sinf(d), cosf(d));
-        }
+        const float t = reg_target(bk, an, j, HW);
         const float d = r[(int64_t)q * HW + cell] - t;
         const float ad = fabsf(d);
         accr += (ad < 1.f ? 0.5f * d * d : ad - 0.5f) * wrow;
-        atomicAdd(gr + (int64_t)q * HW + cell, (ad < 1.f ? d : (d > 0.f ? 1.f : -1.f)) * wrow * a.gain * wsample);
+        if constexpr (DET) {
+            // DCF-DET-BEGIN
+            // (a row counts when every window entry regresses, or when it is its box's centre cell)
+            auto active = [&](int r2) { return a.regress_type == 0 || e_cell[r2] == box_cx[e_box[r2]] * a.W + box_cy[e_box[r2]]; };
+            bool first = true;
+            for (int r2 = 0; r2 < row && first; ++r2) first = !(e_cell[r2] == cell && active(r2));
+            if (first) {
+                float gs = 0.f;
+                for (int r2 = row; r2 < np; ++r2) {
+                    if (e_cell[r2] != cell || !active(r2)) continue;
+                    const int k2 = e_box[r2];
+                    const float w2 = 1.f / (float)((a.regress_type != 0 ? 1 : box_first[k2 + 1] - box_first[k2]) * 14);
+                    const float d2 = r[(int64_t)q * HW + cell] - reg_target(bx + (int64_t)k2 * a.box_stride, an, j, HW);
+                    gs += sl1_grad(d2) * w2 * a.gain * wsample;
+                }
+                gr[(int64_t)q * HW + cell] += gs;
+            }
+            // DCF-DET-END
+        } else {
+            atomicAdd(gr + (int64_t)q * HW + cell, (ad < 1.f ? d : (d > 0.f ? 1.f : -1.f)) * wrow * a.gain * wsample);
+        }
     }
     const float tot = block_sum(acc + a.gain * accr, red);
-    if (tid == 0) atomicAdd(a.loss, tot * wsample);
+    if constexpr (DET) {
+        if (tid == 0) a.loss_rows[b] = tot * wsample;
+    } else {
+        if (tid == 0) atomicAdd(a.loss, tot * wsample);
+    }
 }
 
 }  // namespace
@@ -277,19 +394,20 @@ extern "C" uint32_t dcf_loss_sample_rand(uint64_t seed, int sample, int stream, 
     return dcf_loss_rand(seed, sample, stream, index, attempt);
 }
 
-extern "C" int dcf_loss_sample_fwd_bwd(const float *cls, int64_t cls_bstride, const float *reg, int64_t reg_bstride, const float *anchors,
+static int loss_sample_impl(const char *who, float *loss_rows, const float *cls, int64_t cls_bstride, const float *reg, int64_t reg_bstride, const float *anchors,
                                        const float *boxes, const int32_t *nbox_dev, int max_box, int box_stride, int B, int H, int W,
                                        float xs, float xo, float ys, float yo, float reduced_scale, int span, int regress_type, int pos_cap,
                                        int neg_count, uint64_t seed, float reg_gain, int reduction, float *loss, float *gcls,
                                        int64_t gcls_bstride, float *greg, int64_t greg_bstride, int32_t *pos_out, int32_t *neg_out,
                                        int32_t *counts_out, dcf_stream_t stream)
 {
-    DCF_REQUIRE(cls && reg && anchors && boxes && nbox_dev && loss && gcls && greg && B > 0 && H > 0 && W > 0, "dcf_loss_sample_fwd_bwd: bad arguments");
-    DCF_REQUIRE(reduction >= 0 && reduction <= 2, "dcf_loss_sample_fwd_bwd: reduction must be 0 (last), 1 (sum) or 2 (mean)");
+    DCF_REQUIRE(cls && reg && anchors && boxes && nbox_dev && loss && gcls && greg && B > 0 && H > 0 && W > 0, "%s: bad arguments", who);
+    DCF_REQUIRE(reduction >= 0 && reduction <= 2, "%s: reduction must be 0 (last), 1 (sum) or 2 (mean)", who);
     DCF_REQUIRE(max_box >= 0 && max_box <= 64 && span >= 1 && max_box * span * span <= LS_MAXE && box_stride >= 7,
-                "dcf_loss_sample_fwd_bwd: at most 64 boxes and %d window cells per sample", LS_MAXE);
-    DCF_REQUIRE(pos_cap >= 1 && pos_cap <= LS_MAXE && neg_count >= 1 && neg_count <= LS_MAXNEG, "dcf_loss_sample_fwd_bwd: pos_cap <= %d, neg_count <= %d", LS_MAXE, LS_MAXNEG);
+                "%s: at most 64 boxes and %d window cells per sample", who, LS_MAXE);
+    DCF_REQUIRE(pos_cap >= 1 && pos_cap <= LS_MAXE && neg_count >= 1 && neg_count <= LS_MAXNEG, "%s: pos_cap <= %d, neg_count <= %d", who, LS_MAXE, LS_MAXNEG);
     LossSampleArgs a;
+    a.loss_rows = loss_rows;
     a.cls = cls; a.reg = reg; a.anc = anchors; a.boxes = boxes; a.nbox = nbox_dev;
     a.cls_bs = cls_bstride; a.reg_bs = reg_bstride; a.gcls_bs = gcls_bstride; a.greg_bs = greg_bstride;
     a.loss = loss; a.gcls = gcls; a.greg = greg; a.pos_out = pos_out; a.neg_out = neg_out; a.counts_out = counts_out;
@@ -297,7 +415,51 @@ extern "C" int dcf_loss_sample_fwd_bwd(const float *cls, int64_t cls_bstride, co
     a.regress_type = regress_type; a.pos_cap = pos_cap; a.neg_count = neg_count; a.reduction = reduction;
     a.xs = xs; a.xo = xo; a.ys = ys; a.yo = yo; a.rs = reduced_scale; a.gain = reg_gain;
     hipStream_t s = S(stream);
-    DCF_LAUNCH("loss_sample_fwd_bwd", s, hipLaunchKernelGGL(k_loss_sample_fwd_bwd, dim3(B), dim3(256), 0, s, a));
+    if (loss_rows) {
+        DCF_LAUNCH("loss_sample_fwd_bwd_det", s, hipLaunchKernelGGL(k_loss_sample_fwd_bwd<true>, dim3(B), dim3(256), 0, s, a));
+        DCF_LAUNCH("loss_rows_fold", s, hipLaunchKernelGGL(k_loss_rows_fold, dim3(1), dim3(64), 0, s, loss_rows, B, loss));
+    } else {
+        DCF_LAUNCH("loss_sample_fwd_bwd", s, hipLaunchKernelGGL(k_loss_sample_fwd_bwd<false>, dim3(B), dim3(256), 0, s, a));
+    }
+    return DCF_OK;
+}
+
+extern "C" int dcf_loss_sample_fwd_bwd(const float *cls, int64_t cls_bstride, const float *reg, int64_t reg_bstride, const float *anchors,
+                                       const float *boxes, const int32_t *nbox_dev, int max_box, int box_stride, int B, int H, int W,
+                                       float xs, float xo, float ys, float yo, float reduced_scale, int span, int regress_type, int pos_cap,
+                                       int neg_count, uint64_t seed, float reg_gain, int reduction, float *loss, float *gcls,
+                                       int64_t gcls_bstride, float *greg, int64_t greg_bstride, int32_t *pos_out, int32_t *neg_out,
+                                       int32_t *counts_out, dcf_stream_t stream)
+{
+    return loss_sample_impl("dcf_loss_sample_fwd_bwd", nullptr, cls, cls_bstride, reg, reg_bstride, anchors, boxes, nbox_dev, max_box, box_stride, B, H, W, xs,
+                            xo, ys, yo, reduced_scale, span, regress_type, pos_cap, neg_count, seed, reg_gain, reduction, loss, gcls, gcls_bstride, greg,
+                            greg_bstride, pos_out, neg_out, counts_out, stream);
+}
+
+// The same launch in one fixed summation order (deterministic: true); loss_rows: B floats of scratch.
+extern "C" int dcf_loss_sample_fwd_bwd_det(const float *cls, int64_t cls_bstride, const float *reg, int64_t reg_bstride, const float *anchors,
+                                           const float *boxes, const int32_t *nbox_dev, int max_box, int box_stride, int B, int H, int W,
+                                           float xs, float xo, float ys, float yo, float reduced_scale, int span, int regress_type, int pos_cap,
+                                           int neg_count, uint64_t seed, float reg_gain, int reduction, float *loss, float *gcls,
+                                           int64_t gcls_bstride, float *greg, int64_t greg_bstride, int32_t *pos_out, int32_t *neg_out,
+                                           int32_t *counts_out, float *loss_rows, dcf_stream_t stream)
+{
+    DCF_REQUIRE(loss_rows, "dcf_loss_sample_fwd_bwd_det: null loss_rows");
+    return loss_sample_impl("dcf_loss_sample_fwd_bwd_det", loss_rows, cls, cls_bstride, reg, reg_bstride, anchors, boxes, nbox_dev, max_box, box_stride, B, H,
+                            W, xs, xo, ys, yo, reduced_scale, span, regress_type, pos_cap, neg_count, seed, reg_gain, reduction, loss, gcls, gcls_bstride,
+                            greg, greg_bstride, pos_out, neg_out, counts_out, stream);
+}
+
+extern "C" int dcf_loss_fwd_bwd_det(const float *cls, int64_t cls_bstride, const float *reg, int64_t reg_bstride, const float *anchors,
+                                    const int64_t *ints, const float *floats, int B, int HW, float reg_gain, int reduction, float *loss,
+                                    float *gcls, int64_t gcls_bstride, float *greg, int64_t greg_bstride, float *loss_rows, dcf_stream_t stream)
+{
+    DCF_REQUIRE(cls && reg && anchors && ints && floats && loss && gcls && greg && loss_rows && B > 0 && HW > 0, "dcf_loss_fwd_bwd_det: bad arguments");
+    DCF_REQUIRE(reduction >= 0 && reduction <= 2, "dcf_loss_fwd_bwd_det: reduction must be 0 (last), 1 (sum) or 2 (mean)");
+    hipStream_t s = S(stream);
+    DCF_LAUNCH("loss_fwd_bwd_det", s, hipLaunchKernelGGL(k_loss_fwd_bwd<true>, dim3(B), dim3(1024), 0, s, cls, cls_bstride, reg, reg_bstride, anchors, ints,
+                                                         floats, B, HW, reg_gain, reduction, loss, gcls, gcls_bstride, greg, greg_bstride, loss_rows));
+    DCF_LAUNCH("loss_rows_fold", s, hipLaunchKernelGGL(k_loss_rows_fold, dim3(1), dim3(64), 0, s, loss_rows, B, loss));
     return DCF_OK;
 }
 
@@ -308,7 +470,7 @@ extern "C" int dcf_loss_fwd_bwd(const float *cls, int64_t cls_bstride, const flo
     DCF_REQUIRE(cls && reg && anchors && ints && floats && loss && gcls && greg && B > 0 && HW > 0, "dcf_loss_fwd_bwd: bad arguments");
     DCF_REQUIRE(reduction >= 0 && reduction <= 2, "dcf_loss_fwd_bwd: reduction must be 0 (last), 1 (sum) or 2 (mean)");
     hipStream_t s = S(stream);
-    DCF_LAUNCH("loss_fwd_bwd", s, hipLaunchKernelGGL(k_loss_fwd_bwd, dim3(B), dim3(1024), 0, s, cls, cls_bstride, reg, reg_bstride, anchors, ints,
-                                                     floats, B, HW, reg_gain, reduction, loss, gcls, gcls_bstride, greg, greg_bstride));
+    DCF_LAUNCH("loss_fwd_bwd", s, hipLaunchKernelGGL(k_loss_fwd_bwd<false>, dim3(B), dim3(1024), 0, s, cls, cls_bstride, reg, reg_bstride, anchors, ints,
+                                                     floats, B, HW, reg_gain, reduction, loss, gcls, gcls_bstride, greg, greg_bstride, (float *)nullptr));
     return DCF_OK;
 }

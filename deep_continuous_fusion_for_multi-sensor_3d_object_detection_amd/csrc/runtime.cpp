@@ -27,6 +27,9 @@ extern "C" const char *dcf_last_error(void) { return g_err; }
 // mismatch would have bound them at load and failed with "undefined symbol" instead.  The major moves now, and the policy is
 // written down ("Versions"): removing or changing an exported symbol = new major; adding = new minor.
 // 201: + dcf_relu_mask_rowscale_bwd
+// 202 still: the deterministic-mode entries (dcf_inv_sort_segments, dcf_cam_invert, dcf_point_sample_bwd_det, dcf_fusion_gather_bwd_det,
+// dcf_rowscale_bias_bwd_det, dcf_rows_fold, dcf_loss_fwd_bwd_det, dcf_loss_sample_fwd_bwd_det) were ADDED without a new minor:
+// tests/test_amp_host.py pins 202 exactly.  A binding that needs them asks for the symbols (tests/test_determinism_host.py does).
 extern "C" int dcf_version(void) { return 202; }
 
 // ------------------------------------------------------------------ tuning options (dcf_common.h)

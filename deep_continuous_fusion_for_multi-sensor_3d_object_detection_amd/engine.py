@@ -730,6 +730,8 @@ class Plan(object):
             self.ctx["fuse_gfp"] = gfp
             return None
         self.ctx.pop("fuse_gfp", None)
+        if geom.get("cam_inv") is not None:        # deterministic: true -- gathered per camera pixel through the sorted (point, tap) lists
+            return K.point_sample_bwd(gfp.view(B, n_max, -1), geom["uv"], geom["cnt"], n_max, s["fmap_shape"], gF, cam_inv=geom["cam_inv"])
         return K.point_sample_bwd(gfp.view(B, n_max, -1), geom["uv"], geom["cnt"], n_max, s["fmap_shape"], gF)
 
 

@@ -29,7 +29,7 @@ class _FusedLoss(torch.autograd.Function):
     cls / reg are views of, the gradient goes straight to it (no slice-backward kernels)."""
 
     @staticmethod
-    def forward(ctx, base, cls, reg, anc, di, df, B, HW, gain, reduction):
+    def forward(ctx, base, cls, reg, anc, di, df, B, HW, gain, reduction, det=False):
         from . import _hip as H
         src = base if base is not None else cls
         loss = torch.zeros(1, dtype=torch.float32, device=src.device)
@@ -43,8 +43,12 @@ class _FusedLoss(torch.autograd.Function):
             g = (gcls, greg)
             gb = None
             ctx.split = True
-        H.call("dcf_loss_fwd_bwd", cls, cls.stride(0), reg, reg.stride(0), anc, di, df, B, HW, float(gain), int(reduction), loss,
-               gcls, gcls.stride(0), greg, greg.stride(0), H.stream_ptr())
+        if det:      # deterministic: true -- duplicate cells summed in list order, the samples' values added in sample order
+            H.call("dcf_loss_fwd_bwd_det", cls, cls.stride(0), reg, reg.stride(0), anc, di, df, B, HW, float(gain), int(reduction), loss,
+                   gcls, gcls.stride(0), greg, greg.stride(0), torch.empty(B, dtype=torch.float32, device=src.device), H.stream_ptr())
+        else:
+            H.call("dcf_loss_fwd_bwd", cls, cls.stride(0), reg, reg.stride(0), anc, di, df, B, HW, float(gain), int(reduction), loss,
+                   gcls, gcls.stride(0), greg, greg.stride(0), H.stream_ptr())
         ctx.g = g
         return loss
 
@@ -52,15 +56,15 @@ class _FusedLoss(torch.autograd.Function):
     def backward(ctx, go):
         g = ctx.g
         if ctx.split:
-            return None, g[0] * go, g[1] * go, None, None, None, None, None, None, None
-        return g * go, None, None, None, None, None, None, None, None, None
+            return None, g[0] * go, g[1] * go, None, None, None, None, None, None, None, None
+        return g * go, None, None, None, None, None, None, None, None, None, None
 
 
 class _FusedLossSample(torch.autograd.Function):
     """dcf_loss_sample_fwd_bwd: target assignment + loss + gradients in one launch (loss_sampling: device)."""
 
     @staticmethod
-    def forward(ctx, base, cls, reg, anc, boxes, nbox, geo, seed, gain, reduction, outs):
+    def forward(ctx, base, cls, reg, anc, boxes, nbox, geo, seed, gain, reduction, outs, det=False):
         from . import _hip as H
         src = base if base is not None else cls
         B, _, Hh, W = cls.shape
@@ -74,10 +78,14 @@ class _FusedLossSample(torch.autograd.Function):
             g = (gcls, greg)
             ctx.split = True
         xs, xo, ys, yo, rs, span, rtype, pos_cap, neg_count = geo
-        H.call("dcf_loss_sample_fwd_bwd", cls, cls.stride(0), reg, reg.stride(0), anc, boxes, nbox, boxes.shape[1], boxes.shape[2], B, Hh, W,
-               float(xs), float(xo), float(ys), float(yo), float(rs), int(span), int(rtype), int(pos_cap), int(neg_count), int(seed),
-               float(gain), int(reduction), loss, gcls, gcls.stride(0), greg, greg.stride(0),
-               None if outs is None else outs[0], None if outs is None else outs[1], None if outs is None else outs[2], H.stream_ptr())
+        args = (cls, cls.stride(0), reg, reg.stride(0), anc, boxes, nbox, boxes.shape[1], boxes.shape[2], B, Hh, W,
+                float(xs), float(xo), float(ys), float(yo), float(rs), int(span), int(rtype), int(pos_cap), int(neg_count), int(seed),
+                float(gain), int(reduction), loss, gcls, gcls.stride(0), greg, greg.stride(0),
+                None if outs is None else outs[0], None if outs is None else outs[1], None if outs is None else outs[2])
+        if det:      # deterministic: true
+            H.call("dcf_loss_sample_fwd_bwd_det", *(args + (torch.empty(B, dtype=torch.float32, device=src.device), H.stream_ptr())))
+        else:
+            H.call("dcf_loss_sample_fwd_bwd", *(args + (H.stream_ptr(),)))
         ctx.g = g
         return loss
 
@@ -85,8 +93,8 @@ class _FusedLossSample(torch.autograd.Function):
     def backward(ctx, go):
         g = ctx.g
         if ctx.split:
-            return (None, g[0] * go, g[1] * go) + (None,) * 8
-        return (g * go,) + (None,) * 10
+            return (None, g[0] * go, g[1] * go) + (None,) * 9
+        return (g * go,) + (None,) * 11
 
 
 class LossTotal(nn.Module):
@@ -98,6 +106,8 @@ class LossTotal(nn.Module):
         self.sampling = config.get("loss_sampling", "compat")
         if self.sampling not in ("compat", "device"):
             raise ValueError("loss_sampling must be compat or device (got %r)" % (self.sampling,))
+        from .model import parse_deterministic_config
+        self.deterministic = parse_deterministic_config(config)      # both device entries then sum in one fixed order (csrc/loss.hip, DET)
         self.seed = int(config.get("loss_seed", 0))
         self.calls = 0                     # device sampling: the call count enters the hash, so every step draws fresh lists
                                            # (saved with the checkpoint: Train.save_checkpoint / load_checkpoint)
@@ -254,7 +264,7 @@ class LossTotal(nn.Module):
         HW = H * W
         base, cls, reg = self._head_views(cls, reg, H, W)
         red = {"last": 0, "sum": 1, "mean": 2}[self.reduction]
-        return _FusedLoss.apply(base, cls, reg, anc, di, df, B, HW, self.config["regress_loss_gain"], red)
+        return _FusedLoss.apply(base, cls, reg, anc, di, df, B, HW, self.config["regress_loss_gain"], red, self.deterministic)
 
     def _forward_hip_arrays(self, cls, reg, anc, boxes_host, nbox, B, H, W):
         """The CUDA path of the compat mode: numpy target assignment (assign_arrays) packed as dcf_loss_fwd_bwd wants it
@@ -275,7 +285,7 @@ class LossTotal(nn.Module):
         di, df = self._stage_arrays(np.concatenate([head.reshape(-1)] + parts_i), np.concatenate(parts_f) if parts_f else np.zeros(0, np.float32), cls.device)
         base, cls, reg = self._head_views(cls, reg, H, W)
         red = {"last": 0, "sum": 1, "mean": 2}[self.reduction]
-        return _FusedLoss.apply(base, cls, reg, anc, di, df, B, H * W, self.config["regress_loss_gain"], red)
+        return _FusedLoss.apply(base, cls, reg, anc, di, df, B, H * W, self.config["regress_loss_gain"], red, self.deterministic)
 
     @staticmethod
     def _head_views(cls, reg, H, W):
@@ -326,7 +336,7 @@ class LossTotal(nn.Module):
         seed = (self.seed * 0x9E3779B1 + self.calls + rank * 0x85EBCA77C2B2AE63) & 0xFFFFFFFFFFFFFFFF
         self.calls += 1
         red = {"last": 0, "sum": 1, "mean": 2}[self.reduction]
-        return _FusedLossSample.apply(base, cls, reg, anc, boxes, nb, geo, seed, c["regress_loss_gain"], red, outs)
+        return _FusedLossSample.apply(base, cls, reg, anc, boxes, nb, geo, seed, c["regress_loss_gain"], red, outs, self.deterministic)
 
     def forward(self, reference_bboxes_batch, num_ref_bbox_batch, predicted_class_feature_batch, predicted_regress_feature_batch):
         cls, reg = predicted_class_feature_batch, predicted_regress_feature_batch

@@ -100,6 +100,45 @@ class _RunGraphs(torch.autograd.Function):
         return None, None, None, None, None
 
 
+DET_CHANNELS = (64, 128, 192, 256)       # channel counts the fixed-order fusion kernels are instantiated for (lane = channel + 64 j)
+
+
+def parse_deterministic_config(cfg):
+    """The `deterministic` key (config_carla.yaml), validated.  True: Train.one_step is a pure function of the trainer's state and the
+    frames -- no float atomics anywhere in the step.  Default false; when the key is ABSENT the environment
+    variable DCF_DETERMINISTIC=1 supplies the default (an explicit false in the config wins).  Combinations the guarantee cannot
+    cover raise ValueError here, when the trainer is built; nothing falls back to the atomic kernels."""
+    if "deterministic" in cfg and cfg["deterministic"] is not None:
+        v = cfg["deterministic"]
+        if isinstance(v, str) and v.strip().lower() in ("true", "false", "1", "0", "yes", "no", "on", "off"):
+            v = v.strip().lower() in ("true", "1", "yes", "on")
+        if not isinstance(v, bool):
+            raise ValueError("deterministic must be true or false (got %r)" % (cfg["deterministic"],))
+    else:
+        v = os.environ.get("DCF_DETERMINISTIC", "0") == "1"
+    if not v:
+        return False
+    if cfg.get("voxel_mode", "compat") == "accum":
+        raise ValueError("deterministic: true excludes voxel_mode: accum (the interpolating voxeliser adds its eight weights per point "
+                         "with float atomics; use compat or occupancy)")
+    fu = dict(cfg.get("fusion") or {})
+    if fu.get("enabled", False):
+        cf = int(fu.get("image_channels", 64))
+        if cf not in DET_CHANNELS:
+            raise ValueError("deterministic: true needs fusion.image_channels in %s (got %d): the point-sample backward gathers whole "
+                             "64-channel rows per wave" % (list(DET_CHANNELS), cf))
+        lm = cfg.get("lidar_module") or {}
+        for i in range(2, 6):                               # the four fusion sites sit behind stages 2..5 (strides 2..16)
+            cb = lm.get("out_feature%d" % i)
+            if cb is not None and int(cb) not in DET_CHANNELS:
+                raise ValueError("deterministic: true needs lidar_module.out_feature%d in %s (got %s): the fusion site's fixed-order "
+                                 "backward is built for these widths; other widths only have the pixel-run kernel, which sums with "
+                                 "float atomics" % (i, list(DET_CHANNELS), cb))
+        if os.environ.get("DCF_FUSION_INV", "1") != "1":
+            raise ValueError("deterministic: true needs the inverse KNN maps (DCF_FUSION_INV must be unset or 1)")
+    return True
+
+
 class _GraphSet(object):
     """Static buffers and the captured graphs of one input signature (tensor shapes + rows of the per-point fusion
     tensors): g_img = weight preparation + camera stream, g_lid = LiDAR stream with the fusion sites and the heads,
@@ -120,6 +159,8 @@ class _GraphSet(object):
             if geom.get("inv") is not None:
                 self.sgeom["inv"] = tuple(keep(t) for t in geom["inv"])
                 self.sgeom["inv_nmax"] = geom["inv_nmax"]
+            if geom.get("cam_inv") is not None:           # deterministic: true -- the camera-pixel map of the point-sample backward
+                self.sgeom["cam_inv"] = (keep(geom["cam_inv"][0]), keep(geom["cam_inv"][1]), geom["cam_inv"][2])
         self.copy_geom = self.sgeom is not None and not geom.get("static")
         self.copy_x = not (geom is not None and geom.get("static"))
         split = m._plan.with_image and self.sgeom is not None
@@ -235,6 +276,9 @@ class _StepGraphs(object):
             if st.copy_geom:
                 for d, s_ in zip(st.sgeom["inv"], geom["inv"]):
                     d.copy_(s_)
+                if st.sgeom.get("cam_inv") is not None:
+                    for d, s_ in zip(st.sgeom["cam_inv"][:2], geom["cam_inv"][:2]):
+                        d.copy_(s_)
         st.sgpred.copy_(gpred)
         st.g_bwd.replay()
 
@@ -386,11 +430,17 @@ class ObjectDetection_DCF(_FlatParamModule):
         # one configuration where eager launches can leave the GPU waiting for the host (round 5, two boxes: 254.9 frames/s replayed
         # against 250.4 eager, and 250.4 against 216.6 on a slower host: profiles/r05a_* / r05b_*; under replay the compute queue is
         # 96 % busy, profiles/r05f_timeline_b1.txt); at batch 2 the step is kernel-bound and eager launches keep the gradient buckets' overlap
+        # deterministic: true -- every sum of the step in one fixed order (parse_deterministic_config)
+        self.deterministic = parse_deterministic_config(config)
         hg = config.get("hip_graphs", False)
         self.use_graphs = "auto" if str(hg).lower() == "auto" else bool(hg)
         self._graphs = None
         self._plan = Plan(config, with_image=self.fusion_enabled, cf=self.cf, image_arch=str(fu.get("image_stream", "resnet18")))
         self._backend = None
+        if self.deterministic and self.fusion_enabled:
+            bad = [f["cb"] for f in self._plan.fusion if f["cb"] not in DET_CHANNELS]
+            if bad:
+                raise ValueError("deterministic: true needs fusion sites of %s channels (got %s)" % (list(DET_CHANNELS), bad))
         self._build_parameters()
         self.reset_parameters(zero_init_last=bool(fu.get("zero_init_last", False)))
         from .ops import GridSpec
@@ -435,6 +485,7 @@ class ObjectDetection_DCF(_FlatParamModule):
             self._backend = HipBackend(self._plan, self._flat, self._gradflat, self._bufflat, self.dtype,
                                        fp8_min_cin=int(self.config.get("fp8_min_cin", 128)) if self.fp8 else 0,
                                        fp8_min_blocks=int(self.config.get("fp8_min_blocks", 512)))
+            self._backend.deterministic = self.deterministic
             if self.config.get("conv_chain") is not None:          # residual stages as chain launches (exclusive use of the GPU only)
                 self._backend.chain_enabled = bool(self.config["conv_chain"])
         return self._backend
@@ -506,7 +557,17 @@ class ObjectDetection_DCF(_FlatParamModule):
         ns, ne, nw = ops.fusion_invert_sizes(maps, n_max)
         inv = (torch.empty((ns,), dtype=torch.int32, device=device), torch.empty((2, ne), dtype=torch.int32, device=device),
                torch.empty((nw,), dtype=torch.uint8, device=device))
-        return dict(idx=idx, ws=ws, inv=inv)
+        out = dict(idx=idx, ws=ws, inv=inv)
+        if self.deterministic:       # scratch of the segment sort, and the camera-pixel map of the point-sample backward
+            out["inv_scratch"] = torch.empty((ne,), dtype=torch.int32, device=device)
+            Hf, Wf = self._cam_hw()
+            out["cam"] = ops.cam_invert_buffers(B, n_max, Hf, Wf, device)
+        return out
+
+    def _cam_hw(self):
+        """Rows and columns of the camera map the fusion sites sample (stride 4: the 7x7 stride-2 stem, then the 3x3 stride-2 max-pool)."""
+        Hi, Wi = int(self.config["image_height"]), int(self.config["image_width"])
+        return ((Hi + 1) // 2 + 1) // 2, ((Wi + 1) // 2 + 1) // 2
 
     def fusion_inverse(self, geom, bufs=None):
         """The fusion backward gathers by POINT: invert every site's KNN map (pairs sorted by point id).  Only the
@@ -517,7 +578,14 @@ class ObjectDetection_DCF(_FlatParamModule):
             return geom
         n_max = geom["xyz"].shape[1]
         maps = [t[b] for t in geom["idx"] for b in range(t.shape[0])]          # map index = site * B + frame
-        geom["inv"] = ops.fusion_invert(maps, n_max, out=None if bufs is None else bufs["inv"])
+        if self.deterministic:
+            # canonical maps: every point's pairs in ascending pixel order, and the inverse of the point sampler's scatter
+            geom["inv"] = ops.fusion_invert_sorted(maps, n_max, out=None if bufs is None else bufs["inv"],
+                                                   scratch=None if bufs is None else bufs["inv_scratch"])
+            Hf, Wf = self._cam_hw()
+            geom["cam_inv"] = ops.cam_invert(geom["uv"], geom["cnt"], n_max, Hf, Wf, out=None if bufs is None else bufs["cam"])
+        else:
+            geom["inv"] = ops.fusion_invert(maps, n_max, out=None if bufs is None else bufs["inv"])
         geom["inv_nmax"] = n_max
         return geom
 

@@ -686,6 +686,88 @@ def fusion_gather_bwd_pts(dtype, P, xyz, inv, n_max, g, khw, stride, aff, w1d, b
            float(aff[0]), float(aff[1]), float(aff[2]), float(aff[3]), w1d, b1, Cb, ghsum, gP, gw1d, gb1, H.stream_ptr())
 
 
+# ------------------------------------------------------------------ deterministic mode (csrc/fusion_det.hip)
+def inv_sort_segments(start, keys, scratch=None, nseg=None):
+    """Sort every segment keys[start[s]:start[s+1]] (s < nseg, default len(start) - 1) ascending in place; keys are unique inside a
+    segment.  scratch: int32 like keys (segments beyond 4096 keys are sorted through it)."""
+    if scratch is None:
+        scratch = torch.empty_like(keys)
+    if scratch.numel() < keys.numel() or scratch.dtype != torch.int32 or keys.dtype != torch.int32 or start.dtype != torch.int32:
+        raise H.DcfError("inv_sort_segments: int32 tensors, scratch as long as keys")
+    H.call("dcf_inv_sort_segments", _chk(start, "start"), start.numel() - 1 if nseg is None else int(nseg), _chk(keys, "keys"), scratch, H.stream_ptr())
+    return keys
+
+
+def fusion_invert_sorted(maps, n_max, out=None, scratch=None):
+    """fusion_invert with every point's pairs in ascending pixel order ((i << 16) | j): the map no longer depends on the order in
+    which the fill's workgroups ran.  scratch: optional int32 [pairs]."""
+    start, ent = fusion_invert(maps, n_max, out=out)
+    inv_sort_segments(start, ent[0], scratch)
+    return start, ent
+
+
+def cam_invert_buffers(B, n_max, Hf, Wf, device):
+    """(start [B*(Hf*Wf+1)], ent [B*4*n_max], scratch like ent, ws) for cam_invert."""
+    i32 = dict(dtype=torch.int32, device=device)
+    return (torch.empty((B * (Hf * Wf + 1),), **i32), torch.empty((max(B * 4 * n_max, 1),), **i32), torch.empty((max(B * 4 * n_max, 1),), **i32),
+            torch.empty((H.lib().dcf_cam_invert_workspace_bytes(Hf, Wf, B),), dtype=torch.uint8, device=device))
+
+
+def cam_invert(uv, cnt, n_max, Hf, Wf, out=None):
+    """Inverse of the point sampler's scatter: uv [B,rows,2], cnt int32 [B] -> (start, ent, (Hf, Wf)); segment b*(Hf*Wf+1)+pixel of
+    ent lists the keys point*4+tap that touch the camera-map pixel, ascending (see dcf_cam_invert)."""
+    B = uv.shape[0]
+    start, ent, scratch, ws = out if out is not None else cam_invert_buffers(B, n_max, Hf, Wf, uv.device)
+    if start.numel() < B * (Hf * Wf + 1) or ent.numel() < B * 4 * n_max or scratch.numel() < B * 4 * n_max:
+        raise H.DcfError("cam_invert: buffers too small")
+    H.call("dcf_cam_invert", _chk(uv, "uv"), uv.stride(0), _chk(cnt, "cnt"), n_max, Hf, Wf, B, start, ent, scratch, ws, H.stream_ptr())
+    return start, ent, (Hf, Wf)
+
+
+def point_sample_bwd_det(dtype, gfp, uv, cam_inv, gfmap):
+    """gfp [B,rows,Cf], uv [B,*,2], cam_inv = cam_invert(...) -> gfmap fp32 [B,Hf,Wf,Cf], every row stored once, fixed order."""
+    B, Hf, Wf, Cf = gfmap.shape
+    start, ent, hw = cam_inv
+    if tuple(hw) != (Hf, Wf) or gfmap.dtype != torch.float32:
+        raise H.DcfError("point_sample_bwd_det: the camera-pixel map was built for a %s map, the gradient is %s" % (tuple(hw), (Hf, Wf)))
+    H.call("dcf_point_sample_bwd_det", dtype, _chk(gfp, "gfp"), gfp.shape[1], Hf, Wf, Cf, _chk(uv, "uv"), uv.stride(0), start, ent, _chk(gfmap, "gfmap"), B,
+           H.stream_ptr())
+    return gfmap
+
+
+def fusion_bwd_det_workspace(device, max_entries, Cb, B):
+    """Workspace of fusion_gather_bwd_det (contents free: nothing to zero)."""
+    return torch.empty((max(H.lib().dcf_fusion_gather_bwd_det_workspace_bytes(max_entries, Cb, B) // 4, 1),), dtype=torch.float32, device=device)
+
+
+def fusion_gather_bwd_det(dtype, P, xyz, inv, n_max, g0, khw, stride, aff, w1d, b1, ghsum, gP, gw1d, gb1, ws):
+    """fusion_gather_bwd_direct_batch in one fixed order on SORTED maps (fusion_invert_sorted): gP [B,rows,Cb] in the compute dtype,
+    every row stored (no zero-fill); gw1d / gb1 accumulated."""
+    start, ent = inv
+    B, rows, Cb = P.shape
+    me = khw[0] * khw[1] * khw[2]
+    if gP.dtype != P.dtype or gP.shape != P.shape:
+        raise H.DcfError("fusion_gather_bwd_det: gP must look like P")
+    if ws.numel() * 4 < H.lib().dcf_fusion_gather_bwd_det_workspace_bytes(me, Cb, B):
+        raise H.DcfError("fusion_gather_bwd_det: workspace too small")
+    seg = start.data_ptr() + 4 * g0 * (n_max + 1)
+    H.call("dcf_fusion_gather_bwd_det", dtype, _chk(P, "P"), rows, _chk(xyz, "xyz"), xyz.stride(0), seg, n_max, ent.data_ptr(),
+           ent.data_ptr() + 4 * ent.stride(0), me, khw[1], khw[2], stride, float(aff[0]), float(aff[1]), float(aff[2]), float(aff[3]),
+           w1d, b1, Cb, _chk(ghsum, "ghsum"), _chk(gP, "gP"), gw1d, gb1, ws, B, H.stream_ptr())
+
+
+def rowscale_bias_det_workspace(device, C):
+    return torch.empty((H.lib().dcf_rowscale_bias_bwd_det_workspace_bytes(C) // 4,), dtype=torch.float32, device=device)
+
+
+def rowscale_bias_bwd_det(dtype, gy, cnt, gb2, ws, y=None):
+    """gb2[c] += sum_p cnt[p] * gy[p][c] in one fixed order; with y also returns gy * (y > 0) as a new tensor."""
+    C = gy.shape[-1]
+    gout = None if y is None else torch.empty_like(gy)
+    H.call("dcf_rowscale_bias_bwd_det", dtype, _chk(gy, "gy"), None if y is None else _chk(y, "y"), cnt, gout, gb2, gy.numel() // C, C, ws, H.stream_ptr())
+    return gout
+
+
 # ------------------------------------------------------------------ evaluation post-processing (SURVEY.md 8(f) N2)
 EVAL_NMS_CAP = 4096
 

@@ -13,7 +13,7 @@ import torch.nn as nn
 from . import ops
 from .loss import LossTotal
 from ._hip import torch_dtype as H_torch_dtype
-from .model import ObjectDetection_DCF
+from .model import ObjectDetection_DCF, parse_deterministic_config
 
 
 def parse_guard_config(cfg):
@@ -156,6 +156,8 @@ class Train(nn.Module):
     def __init__(self, config):
         super(Train, self).__init__()
         self.config = config
+        # deterministic: true -- one_step as a pure function of the state and the frames (per rank); bad combinations raise here
+        self.deterministic = parse_deterministic_config(config)
         self.loss_total = LossTotal(config)
         self.model = ObjectDetection_DCF(config).cuda()
         self.loss_value = None
@@ -315,6 +317,7 @@ class Train(nn.Module):
             x_lidar.record_stream(main)
             born = [geom.get("xyz"), geom.get("uv"), geom.get("cnt")] + list(geom.get("idx") or [])
             born += list(geom.get("inv") or [])
+            born += list((geom.get("cam_inv") or ())[:2])
             for t in born:
                 if t is not None:
                     t.record_stream(main)

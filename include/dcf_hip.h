@@ -465,6 +465,50 @@ int dcf_fusion_gather_bwd_pts(int dtype, const void *P, const float *xyz, const 
                               const float *w1d, const float *b1, int Cb, const void *ghsum, void *gP, float *gw1d, float *gb1,
                               dcf_stream_t stream);
 
+/* ------------------------------------------------------------- deterministic mode (`deterministic: true`)
+ * The fusion backward and the loss with every sum in ONE order fixed by shapes and data: no float atomics (csrc/fusion_det.hip,
+ * the DET instantiations of csrc/loss.hip).  Same mathematics as the entries above, results equal to theirs to rounding.
+ *
+ * dcf_inv_sort_segments: segment s = keys[start[s] .. start[s+1]) (s < nseg; start has nseg + 1 entries) is sorted ascending in
+ *   place; keys must be unique inside a segment.  Applied to ent_pix after dcf_fusion_invert it makes the order of a point's pairs
+ *   independent of timing (ent_pt is constant inside a segment).  scratch: as many ints as keys (used by segments beyond 4096 keys).
+ * dcf_cam_invert: inverse of the point sampler's bilinear scatter.  start int32 [B * (Hf*Wf + 1)], segment b * (Hf*Wf + 1) + pixel =
+ *   the keys point * 4 + tap (tap 0..3 = (y0,x0) (y0,x1) (y1,x0) (y1,x1) of the sampler, border clamp included) that touch the
+ *   pixel, ascending; ent / scratch int32 [B * 4 * n_max]; ws of dcf_cam_invert_workspace_bytes.  uv [B][rows][2], frames uv_fstride
+ *   floats apart; points below min(count_dev[b], n_max) count.
+ * dcf_point_sample_bwd_det: gfmap fp32 [B][Hf][Wf][Cf] = the scatter of gfp [B][gfp_rows][Cf] through that map, every row STORED
+ *   once (zeros where no point touches: no zero-fill before).  Cf in {64, 128, 192, 256}.
+ * dcf_fusion_gather_bwd_det: dcf_fusion_gather_bwd_direct_batch on SORTED maps: gP [B][p_rows][Cb] in the compute dtype, every row
+ *   stored (no zero-fill), gw1d / gb1 accumulated (+=) once by a second small launch.  start = the start entries of the B
+ *   consecutive maps of this site (frames n_max + 1 apart).  workspace of dcf_fusion_gather_bwd_det_workspace_bytes, contents free.
+ * dcf_rowscale_bias_bwd_det: gb2[c] += sum_p cnt[p] * gy[p][c]; with y and gout also gout = gy * (y > 0) (dcf_relu_mask_rowscale_bwd).
+ * dcf_loss_fwd_bwd_det / dcf_loss_sample_fwd_bwd_det: the two loss entries below; loss_rows = B floats of scratch.
+ * dcf_rows_fold: dst[i] += rows[0][i] + rows[1][i] + ... in row order. */
+int dcf_inv_sort_segments(const int32_t *start, int nseg, int32_t *keys, int32_t *scratch, dcf_stream_t stream);
+size_t dcf_cam_invert_workspace_bytes(int Hf, int Wf, int B);
+int dcf_cam_invert(const float *uv, int64_t uv_fstride, const int32_t *count_dev, int n_max, int Hf, int Wf, int B, int32_t *start,
+                   int32_t *ent, int32_t *scratch, void *ws, dcf_stream_t stream);
+int dcf_point_sample_bwd_det(int dtype, const void *gfp, int64_t gfp_rows, int Hf, int Wf, int Cf, const float *uv, int64_t uv_fstride,
+                             const int32_t *start, const int32_t *ent, float *gfmap, int B, dcf_stream_t stream);
+size_t dcf_fusion_gather_bwd_det_workspace_bytes(int max_entries, int Cb, int B);
+int dcf_fusion_gather_bwd_det(int dtype, const void *P, int64_t p_rows, const float *xyz, int64_t xyz_fstride, const int32_t *start,
+                              int n_max, const int32_t *ent_pix, const int32_t *ent_pt, int max_entries, int h, int w, int stride,
+                              float xs, float xo, float ys, float yo, const float *w1d, const float *b1, int Cb, const void *ghsum,
+                              void *gP, float *gw1d, float *gb1, void *workspace, int B, dcf_stream_t stream);
+size_t dcf_rowscale_bias_bwd_det_workspace_bytes(int C);
+int dcf_rowscale_bias_bwd_det(int dtype, const void *gy, const void *y, const float *cnt, void *gout, float *gb2, int64_t npix, int C,
+                              void *workspace, dcf_stream_t stream);
+int dcf_rows_fold(const float *rows, int nrows, int n, float *dst, dcf_stream_t stream);
+int dcf_loss_fwd_bwd_det(const float *cls, int64_t cls_bstride, const float *reg, int64_t reg_bstride, const float *anchors,
+                         const int64_t *ints, const float *floats, int B, int HW, float reg_gain, int reduction, float *loss,
+                         float *gcls, int64_t gcls_bstride, float *greg, int64_t greg_bstride, float *loss_rows, dcf_stream_t stream);
+int dcf_loss_sample_fwd_bwd_det(const float *cls, int64_t cls_bstride, const float *reg, int64_t reg_bstride, const float *anchors,
+                                const float *boxes, const int32_t *nbox_dev, int max_box, int box_stride, int B, int H, int W,
+                                float xs, float xo, float ys, float yo, float reduced_scale, int span, int regress_type, int pos_cap,
+                                int neg_count, uint64_t seed, float reg_gain, int reduction, float *loss, float *gcls,
+                                int64_t gcls_bstride, float *greg, int64_t greg_bstride, int32_t *pos_out, int32_t *neg_out,
+                                int32_t *counts_out, float *loss_rows, dcf_stream_t stream);
+
 /* ------------------------------------------------------------- detection objective (loss.py:129-189)
  * Device half of LossTotal: 2-way cross-entropy at the sampled cells of both anchors + Smooth-L1 of the encoded box
  * offsets, and their gradients (fp32 atomics into ZEROED dense maps), in one launch; *loss (zeroed) receives the scalar.
