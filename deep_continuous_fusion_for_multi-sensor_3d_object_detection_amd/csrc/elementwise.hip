@@ -1271,7 +1271,7 @@ extern "C" int dcf_maxpool3x3s2_fwd_idx(int dtype, const void *x, void *y, uint3
 extern "C" int dcf_maxpool3x3s2_bwd_idx(int dtype, const uint32_t *idx, const void *gy, void *gx, int B, int H, int W, int Ho, int Wo, int C,
                                         dcf_stream_t stream)
 {
-    DCF_REQUIRE(idx && gy && gx && C % 4 == 0, "dcf_maxpool3x3s2_bwd_idx: bad arguments");
+    DCF_REQUIRE(idx && gy && gx && C % 4 == 0 && Ho == (H - 1) / 2 + 1 && Wo == (W - 1) / 2 + 1, "dcf_maxpool3x3s2_bwd_idx: bad arguments");
     const int64_t total = (int64_t)B * H * W * (C / 4);
     hipStream_t s = S(stream);
     DCF_DISPATCH_DTYPE(dtype, { DCF_LAUNCH_B("maxpool_bwd", ((double)B * Ho * Wo * C + (double)total * 4) * sizeof(T), s, hipLaunchKernelGGL(k_maxpool_bwd_idx<T>, dim3(cdiv(total, 256)), dim3(256), 0, s, idx, (const T *)gy, (T *)gx, B, H, W, Ho, Wo, C / 4)); })
@@ -1281,7 +1281,7 @@ extern "C" int dcf_maxpool3x3s2_bwd_idx(int dtype, const uint32_t *idx, const vo
 extern "C" int dcf_maxpool3x3s2_bwd(int dtype, const void *x, const void *y, const void *gy, void *gx, int B, int H, int W,
                                     int Ho, int Wo, int C, dcf_stream_t stream)
 {
-    DCF_REQUIRE(x && gy && gx && C % 4 == 0, "dcf_maxpool3x3s2_bwd: bad arguments");
+    DCF_REQUIRE(x && gy && gx && C % 4 == 0 && Ho == (H - 1) / 2 + 1 && Wo == (W - 1) / 2 + 1, "dcf_maxpool3x3s2_bwd: bad arguments");
     const int64_t total = (int64_t)B * H * W * (C / 4);
     hipStream_t s = S(stream);
     DCF_DISPATCH_DTYPE(dtype, {

@@ -308,7 +308,8 @@ int dcf_resize_bilinear_fwd(int dtype, const void *x, const void *add, void *y, 
 /* gx = resize^T(gy): gather form (each input pixel sums its contributing output pixels). */
 int dcf_resize_bilinear_bwd(int dtype, const void *gy, void *gx, int B, int Hi, int Wi, int Ho, int Wo, int C,
                             int align_corners, dcf_stream_t stream);
-/* 3x3/2 max-pool pad 1 (image stem), NHWC; bwd routes to the first arg-max in scan order. */
+/* 3x3/2 max-pool pad 1 (image stem), NHWC; bwd routes to the first arg-max in scan order.  Every entry, forward and
+ * backward, requires Ho == (H - 1) / 2 + 1 and Wo == (W - 1) / 2 + 1. */
 int dcf_maxpool3x3s2_fwd(int dtype, const void *x, void *y, int B, int H, int W, int Ho, int Wo, int C,
                          dcf_stream_t stream);
 int dcf_maxpool3x3s2_bwd(int dtype, const void *x, const void *y, const void *gy, void *gx, int B, int H, int W,

@@ -153,6 +153,82 @@ def test_maxpool(dtype):
         assert torch.equal(ops.maxpool_bwd_idx(dtype, idx, to_dev(gy, dtype), tuple(xd.shape)), gx)
 
 
+def _post_relu(shape, seed, dtype):
+    """What the pool sees in production, the output of a ReLU: relu(u - 0.2) with u uniform in +-1, so about 60 % of the values
+    are exact zeros and whole windows tie at 0; channel 0 all zero, channel 1 constant at 1.0 (every window ties at its
+    maximum).  Zeros alone leave too few tied windows (0.6^9 = 1 % of the whole windows of a random channel, well under the
+    30 % asserted below once there are 64 channels), and none whose tied maximum is not 0: so three channels of four are
+    rounded to steps of 0.5, 0.5 and 0.25 (exact in every storage type), where the non-zero levels tie as well."""
+    x = torch.relu(rnd(shape, seed) - 0.2)
+    step = torch.tensor([0.5, 0.5, 0.25, 0.0])[torch.arange(shape[1]) % 4].view(1, -1, 1, 1)
+    x = torch.where(step > 0, torch.round(x / step.clamp(min=0.25)) * step, x)
+    x[:, 0] = 0.0
+    x[:, 1] = 1.0
+    return q(x, dtype)
+
+
+@pytest.mark.parametrize("C", [4, 64])
+@pytest.mark.parametrize("dtype", [0, 1, 2])
+def test_maxpool_post_relu_ties(dtype, C):
+    """Tied windows decide where the gradient goes: the first maximum in scan order (dh, then dw), as ATen routes it.  Forward
+    equal to F.max_pool2d; the recorded position byte against a numpy arg-max (first occurrence) of the unfolded windows; the
+    three backward routes equal to each other, within TOL of autograd, and for fp32 with an integer-valued gy EQUAL to autograd
+    (small integer sums are exact, so a gradient sent to the wrong tied pixel cannot hide in a tolerance)."""
+    ops = pkg("ops")
+    tied = total = 0
+    for (hh, ww) in ((1, 1), (2, 3), (5, 4), (12, 16), (19, 31)):
+        x = _post_relu((2, C, hh, ww), 100 + hh, dtype).requires_grad_(True)
+        assert 0.5 < float((x[:, 2:] == 0).float().mean()) < 0.8 or hh * ww < 20
+        ref = F.max_pool2d(x, 3, 2, 1)
+        Ho, Wo = ref.shape[2:]
+        # the windows unfolded in scan order; positions outside the image never win
+        win = F.unfold(F.pad(x.detach(), (1, 1, 1, 1), value=float("-inf")), 3, stride=2).view(2, C, 9, Ho, Wo).numpy()
+        first = win.argmax(2)                                                # numpy: the first occurrence of the maximum
+        assert np.array_equal(win.max(2), ref.detach().numpy())
+        if hh * ww > 1:                                                      # (a 1 x 1 image has one-element windows)
+            tied += int(((win == win.max(2, keepdims=True)).sum(2) > 1).sum())
+            total += first.size
+        xd = to_dev(x.detach(), dtype)
+        y = ops.maxpool_fwd(dtype, xd)
+        assert torch.equal(from_dev(y), ref.detach()), (hh, ww)
+        y2, idx = ops.maxpool_fwd_idx(dtype, xd)
+        assert torch.equal(y2, y), (hh, ww)
+        got = idx.cpu().numpy().view(np.uint8).reshape(2, Ho, Wo, C).transpose(0, 3, 1, 2)
+        assert np.array_equal(got, first), (hh, ww)
+        gys = [q(rnd(tuple(ref.shape), 11), dtype)]
+        if dtype == 0:
+            gys.append(torch.randint(-3, 4, tuple(ref.shape), generator=torch.Generator().manual_seed(12)).float())
+        for n, gy in enumerate(gys):
+            x.grad = None
+            ref.backward(gy, retain_graph=True)
+            gd = to_dev(gy, dtype)
+            gx = ops.maxpool_bwd(dtype, xd, y, gd)                           # tie scan over the earlier window positions
+            assert torch.equal(ops.maxpool_bwd(dtype, xd, None, gd), gx), (hh, ww)            # arg-max recomputed per window
+            assert torch.equal(ops.maxpool_bwd_idx(dtype, idx, gd, tuple(xd.shape)), gx), (hh, ww)      # gather by the recorded byte
+            if n == 1:
+                assert torch.equal(from_dev(gx), x.grad), (hh, ww)
+            else:
+                assert rel_err(from_dev(gx), x.grad) < TOL[dtype], (hh, ww)
+    assert tied >= 0.3 * total, "tied windows: %d of %d" % (tied, total)
+
+
+def test_maxpool_bwd_bad_output_size_fails_loudly():
+    """The backward entries take Ho / Wo from the caller: a pair that does not belong to H / W is an error, not a read out of bounds."""
+    ops, Hm = pkg("ops"), pkg("_hip")
+    x = to_dev(_post_relu((2, 4, 12, 16), 3, 0), 0)
+    y, idx = ops.maxpool_fwd_idx(0, x)
+    for shape in ((2, 7, 8, 4), (2, 6, 9, 4), (2, 5, 8, 4)):
+        gy = torch.zeros(shape, device="cuda")
+        with pytest.raises(Hm.DcfError):
+            ops.maxpool_bwd(0, x, y, gy)
+        with pytest.raises(Hm.DcfError):
+            ops.maxpool_bwd(0, x, None, gy)
+        with pytest.raises(Hm.DcfError):
+            ops.maxpool_bwd_idx(0, idx, gy, tuple(x.shape))
+    gy = torch.ones((2, 6, 8, 4), device="cuda")
+    assert torch.equal(ops.maxpool_bwd(0, x, y, gy), ops.maxpool_bwd_idx(0, idx, gy, tuple(x.shape)))
+
+
 @pytest.mark.parametrize("dtype", [0, 1, 2])
 def test_head_fwd_bwd(dtype):
     """softmax pairs + box decode + concat against the restated model.py:116-137,168-172,204."""

@@ -133,6 +133,38 @@ def test_loss_restatement_seeded():
         assert float(cls.grad[0].abs().max()) == 0.0  # F5: only the last sample contributes
 
 
+def test_loss_from_lists_seeded():
+    """The float64, list-driven statement (what the device loss kernels are held against) fed with sample_positions' lists
+    reproduces the imported reference's seeded loss and gradients; 'sum' / 'mean' add up the per-sample 'last' values."""
+    z = load_golden("loss.npz")
+    cfg = golden_cfg(load_golden("model_tiny.npz"))
+    anc = model_ref.anchors(cfg)
+    cls, reg = torch.from_numpy(z["cls"]), torch.from_numpy(z["reg"])
+    bboxes, nbox = torch.from_numpy(z["bboxes"]), torch.from_numpy(z["nbox"])
+    B, _, H, W = cls.shape
+    for seed in (0, 1):
+        np.random.seed(seed)
+        lists, boxes = [], []
+        for b in range(B):
+            bx = bboxes[b, :int(nbox[b])]
+            lists.append(loss_ref.lists_from_positions(*loss_ref.sample_positions(cfg, bx, H, W), W))
+            boxes.append(bx.numpy())
+        val, gcls, greg = loss_ref.loss_from_lists(cls, reg, anc, lists, boxes, cfg["regress_loss_gain"], "last")
+        assert val.dtype == gcls.dtype == greg.dtype == torch.float64
+        assert abs(val.item() - float(z["loss_seed%d" % seed])) < 1e-6
+        assert np.abs(gcls.numpy() - z["gcls_seed%d" % seed]).max() < 2e-7
+        assert np.abs(greg.numpy() - z["greg_seed%d" % seed]).max() < 2e-7
+        assert float(gcls[:-1].abs().max()) == 0.0 and float(greg[:-1].abs().max()) == 0.0
+        # the other reductions: the sum of every sample's own 'last' value (the batch cut to end at that sample)
+        each = [loss_ref.loss_from_lists(cls[:b + 1], reg[:b + 1], anc, lists[:b + 1], boxes[:b + 1], cfg["regress_loss_gain"], "last")
+                for b in range(B)]
+        tot, gc, gr = loss_ref.loss_from_lists(cls, reg, anc, lists, boxes, cfg["regress_loss_gain"], "sum")
+        assert abs(tot.item() - sum(e[0].item() for e in each)) < 1e-12
+        assert all(float((gc[b] - each[b][1][b]).abs().max()) < 1e-15 for b in range(B))
+        mean = loss_ref.loss_from_lists(cls, reg, anc, lists, boxes, cfg["regress_loss_gain"], "mean")
+        assert abs(mean[0].item() - tot.item() / B) < 1e-12 and float((mean[2] - gr / B).abs().max()) < 1e-15
+
+
 def test_full_carla_cfg1():
     """BASELINE configs[0]: 10k-pt CARLA frame through the (restated) reference model on CPU."""
     g = load_golden("geometry_carla.npz")
