@@ -202,6 +202,212 @@ __host__ __device__ inline uint32_t dcf_loss_rand(uint64_t seed, int sample, int
 constexpr int LS_MAXE = 1024;       // positive entries per sample (max_box * span^2)
 constexpr int LS_MAXNEG = 512;
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Hard negative mining ("loss_sampling: hard"): the negatives of a sample are the neg_count cells outside
+// every positive window with the highest key, key(cell) = max over the two anchors of ord(s1 - s0) -- ord = the order-preserving
+// map from fp32 to unsigned, so everything below is integer work and agrees with the host statement (loss.py, hard_negatives)
+// bit for bit.  Window cells get key 0 and candidates at least 1 (the two keys that moves are NaN patterns), so "k-th largest
+// over the whole map" never lands on a window cell while k <= number of candidates.
+//
+// An exact radix select, 8 bits per pass, G workgroups per sample over contiguous chunks of the map:
+//   k_hard_keys          keys -> workspace, per-workgroup histogram of the top digit, per-workgroup candidate count
+//   k_hard_pass  x 3     every workgroup folds the G histograms of the pass before, finds the digit that holds the k-th largest
+//                        key, and builds its histogram of the next digit over the cells that match the prefix so far
+//   k_hard_compact       last digit -> the cut key; cells above it go to the list through an integer cursor (their order is
+//                        settled later), of the cells equal to it the r lowest-index ones: a workgroup knows how many ties the
+//                        chunks before its own hold from their histograms, and walks its own chunk in order
+//   k_loss_sample_fwd_bwd<DET, true>  ranks the <= 512 survivors by (key descending, cell ascending) and does the terms
+// Histograms are built with integer LDS atomics and STORED per workgroup, never merged with global atomics: nothing here depends
+// on scheduling, and the workspace needs no clearing between calls (the cursor is reset by k_hard_keys).
+//
+// per-sample workspace, in ints:
+constexpr int HS_CURSOR = 0;                    // list cursor of the cells above the cut
+constexpr int HS_STATE = 1;                     // (prefix, k remaining) after pass 1, 2, 3: 6 ints
+constexpr int HS_K = 7;                         // nneg = min(neg_count, candidates)
+constexpr int HS_CNT = 16;                      // candidates per workgroup [HARD_MAXG]
+constexpr int HARD_MAXG = 64;
+constexpr int HS_LIST = HS_CNT + HARD_MAXG;     // survivors [LS_MAXNEG]
+constexpr int HS_HIST = HS_LIST + LS_MAXNEG;    // two sets of [HARD_MAXG][256] histograms, used in turn
+constexpr int HS_KEYS = HS_HIST + 2 * HARD_MAXG * 256;      // keys [HW]
+constexpr int HARD_THREADS = 256;
+
+__host__ __device__ inline int64_t hard_ws_stride(int HW) { return ((int64_t)HS_KEYS + HW + 3) & ~(int64_t)3; }
+// cells per workgroup: a multiple of the workgroup, at least 1024, and no more than HARD_MAXG chunks per sample
+__host__ __device__ inline int hard_chunk(int HW)
+{
+    const int per = (HW + HARD_MAXG - 1) / HARD_MAXG;
+    const int up = (per + HARD_THREADS - 1) / HARD_THREADS * HARD_THREADS;
+    return up > 1024 ? up : 1024;
+}
+
+__device__ __forceinline__ unsigned hard_ord(float d)
+{
+    const unsigned u = __float_as_uint(d);
+    return (u & 0x80000000u) ? ~u : (u ^ 0x80000000u);
+}
+
+struct HardArgs {
+    const float *cls, *boxes;
+    const int32_t *nbox;
+    int64_t cls_bs, ws_stride;
+    int32_t *ws;
+    int max_box, box_stride, b0, H, W, span, neg_count, G, chunk;
+    float xs, xo, ys, yo, rs;
+};
+
+// Folds the G per-workgroup histograms at `hist` and finds the digit d with count(digit > d) < kr <= count(digit >= d); returns d and
+// leaves kr - count(digit > d) in *kr_out.  kr == 0 (no candidates): digit 0, kr 0.  All HARD_THREADS threads call it.
+__device__ __forceinline__ int hard_pick_digit(const int32_t *hist, int G, int kr, int *s_suf, int *s_pick, int *kr_out)
+{
+    const int t = threadIdx.x;
+    int tot = 0;
+    for (int g = 0; g < G; ++g) tot += hist[g * 256 + t];
+    if (t == 0) { s_pick[0] = 0; s_pick[1] = 0; }
+    s_suf[t] = tot;
+    __syncthreads();
+    for (int off = 1; off < 256; off <<= 1) {                     // s_suf[t] = count(digit >= t)
+        const int v = t + off < 256 ? s_suf[t + off] : 0;
+        __syncthreads();
+        s_suf[t] += v;
+        __syncthreads();
+    }
+    const int above = t + 1 < 256 ? s_suf[t + 1] : 0;
+    if (kr > 0 && s_suf[t] >= kr && above < kr) { s_pick[0] = t; s_pick[1] = kr - above; }      // (one thread at most: s_suf falls with t)
+    __syncthreads();
+    *kr_out = s_pick[1];
+    return s_pick[0];
+}
+
+__global__ void __launch_bounds__(HARD_THREADS) k_hard_keys(HardArgs a)
+{
+    __shared__ int hist[256];
+    __shared__ int box_cx[64], box_cy[64];
+    __shared__ int s_cnt;
+    const int g = blockIdx.x, b = a.b0 + blockIdx.y, tid = threadIdx.x;
+    const int HW = a.H * a.W, half = a.span / 2;
+    const int nb = min(a.nbox[b], a.max_box);
+    const float *bx = a.boxes + (int64_t)b * a.max_box * a.box_stride;
+    int32_t *ws = a.ws + (int64_t)b * a.ws_stride;
+    hist[tid] = 0;
+    if (tid == 0) s_cnt = 0;
+    if (tid < nb) {
+        // the centre cell exactly as k_loss_sample_fwd_bwd computes it; a box outside the map has no window
+        const int cx = (int)(__fdiv_rn(__fadd_rn(__fmul_rn(bx[tid * a.box_stride], a.xs), a.xo), a.rs));
+        const int cy = (int)(__fdiv_rn(__fadd_rn(__fmul_rn(bx[tid * a.box_stride + 1], a.ys), a.yo), a.rs));
+        const bool in = !(cx < 0 || cx > a.H - 1 || cy < 0 || cy > a.W - 1);
+        box_cx[tid] = in ? cx : -1000000; box_cy[tid] = in ? cy : 0;
+    }
+    __syncthreads();
+    const float *c = a.cls + b * a.cls_bs;
+    unsigned *keys = (unsigned *)(ws + HS_KEYS);
+    const int lo = g * a.chunk, hi = min(lo + a.chunk, HW);
+    int cnt = 0;
+    for (int cell = lo + tid; cell < hi; cell += HARD_THREADS) {
+        const int px = cell / a.W, py = cell - px * a.W;
+        bool window = false;
+        for (int k = 0; k < nb; ++k) {
+            const int dx = px - (box_cx[k] - half), dy = py - (box_cy[k] - half);
+            window |= dx >= 0 && dx < a.span && dy >= 0 && dy < a.span;
+        }
+        unsigned key = 0;
+        if (!window) {
+            const unsigned k0 = hard_ord(__fsub_rn(c[(int64_t)HW + cell], c[cell]));
+            const unsigned k1 = hard_ord(__fsub_rn(c[(int64_t)3 * HW + cell], c[(int64_t)2 * HW + cell]));
+            key = max(max(k0, k1), 1u);
+            ++cnt;
+        }
+        keys[cell] = key;
+        atomicAdd(&hist[key >> 24], 1);
+    }
+    if (cnt) atomicAdd(&s_cnt, cnt);
+    __syncthreads();
+    ws[HS_HIST + g * 256 + tid] = hist[tid];
+    if (tid == 0) {
+        ws[HS_CNT + g] = s_cnt;
+        if (g == 0) ws[HS_CURSOR] = 0;
+    }
+}
+
+// pass p = 1, 2, 3 (digit shift 24 - 8p)
+__global__ void __launch_bounds__(HARD_THREADS) k_hard_pass(HardArgs a, int p)
+{
+    __shared__ int hist[256], s_suf[256];
+    __shared__ int s_pick[2];
+    const int g = blockIdx.x, b = a.b0 + blockIdx.y, tid = threadIdx.x;
+    const int HW = a.H * a.W;
+    int32_t *ws = a.ws + (int64_t)b * a.ws_stride;
+    unsigned prefix = 0;
+    int kr;
+    if (p == 1) {
+        int ncand = 0;
+        for (int i = 0; i < a.G; ++i) ncand += ws[HS_CNT + i];
+        kr = min(a.neg_count, ncand);
+    } else {
+        prefix = (unsigned)ws[HS_STATE + 2 * (p - 2)];
+        kr = ws[HS_STATE + 2 * (p - 2) + 1];
+    }
+    hist[tid] = 0;
+    const int shift = 24 - 8 * p;
+    const int d = hard_pick_digit(ws + HS_HIST + ((p - 1) & 1) * HARD_MAXG * 256, a.G, kr, s_suf, s_pick, &kr);
+    prefix |= (unsigned)d << (shift + 8);
+    if (g == 0 && tid == 0) { ws[HS_STATE + 2 * (p - 1)] = (int)prefix; ws[HS_STATE + 2 * (p - 1) + 1] = kr; }
+    const unsigned *keys = (const unsigned *)(ws + HS_KEYS);
+    const int lo = g * a.chunk, hi = min(lo + a.chunk, HW);
+    for (int cell = lo + tid; cell < hi; cell += HARD_THREADS) {
+        const unsigned key = keys[cell];
+        if ((key >> (shift + 8)) == (prefix >> (shift + 8))) atomicAdd(&hist[(key >> shift) & 255u], 1);
+    }
+    __syncthreads();
+    ws[HS_HIST + (p & 1) * HARD_MAXG * 256 + g * 256 + tid] = hist[tid];
+}
+
+__global__ void __launch_bounds__(HARD_THREADS) k_hard_compact(HardArgs a)
+{
+    __shared__ int s_suf[256];
+    __shared__ int s_pick[2];
+    __shared__ int s_wave[HARD_THREADS / 64];
+    const int g = blockIdx.x, b = a.b0 + blockIdx.y, tid = threadIdx.x;
+    const int HW = a.H * a.W;
+    int32_t *ws = a.ws + (int64_t)b * a.ws_stride;
+    const int32_t *hist = ws + HS_HIST + HARD_MAXG * 256;          // pass 3's histograms: the last digit of the cells that match 24 bits
+    int r;
+    const int d = hard_pick_digit(hist, a.G, ws[HS_STATE + 5], s_suf, s_pick, &r);
+    const unsigned cut = (unsigned)ws[HS_STATE + 4] | (unsigned)d;
+    int ncand = 0;
+    for (int i = 0; i < a.G; ++i) ncand += ws[HS_CNT + i];
+    const int k = min(a.neg_count, ncand);
+    if (g == 0 && tid == 0) ws[HS_K] = k;
+    if (k == 0) return;
+    const int above = k - r;                        // cells with a key above the cut: slots [0, above) through the cursor
+    int tie_base = 0;                               // ties in the chunks before this one
+    for (int i = 0; i < g; ++i) tie_base += hist[i * 256 + d];
+    const unsigned *keys = (const unsigned *)(ws + HS_KEYS);
+    int32_t *list = ws + HS_LIST;
+    const int lo = g * a.chunk, hi = min(lo + a.chunk, HW);
+    for (int t0 = lo; t0 < hi; t0 += HARD_THREADS) {               // tiles in cell order
+        const int cell = t0 + tid;
+        const unsigned key = cell < hi ? keys[cell] : 0u;          // (cut >= 1: key 0 is neither above nor a tie)
+        if (key > cut) {
+            const int slot = atomicAdd(&ws[HS_CURSOR], 1);
+            if (slot < above) list[slot] = cell;
+        }
+        const bool tie = key == cut;
+        const unsigned long long m = __ballot(tie);
+        const int lane = tid & 63, wv = tid >> 6;
+        __syncthreads();                                           // (s_wave of the tile before has been read)
+        if (lane == 0) s_wave[wv] = __popcll(m);
+        __syncthreads();
+        int before = tie_base + __popcll(m & ((1ull << lane) - 1ull));
+        int tile_ties = 0;
+        for (int w = 0; w < HARD_THREADS / 64; ++w) {
+            if (w < wv) before += s_wave[w];
+            tile_ties += s_wave[w];
+        }
+        if (tie && before < r) list[above + before] = cell;
+        tie_base += tile_ties;
+    }
+}
+
 struct LossSampleArgs {
     const float *cls, *reg, *anc, *boxes;
     const int32_t *nbox;
@@ -211,9 +417,13 @@ struct LossSampleArgs {
     uint64_t seed;
     int max_box, box_stride, B, H, W, span, regress_type, pos_cap, neg_count, reduction;
     float xs, xo, ys, yo, rs, gain;
+    // loss_sampling: hard -- the mined negatives of samples >= hard_b0 wait in the workspace (k_hard_* below)
+    const int32_t *hard_ws;
+    int64_t hard_stride;
+    int hard_b0;
 };
 
-template <bool DET>
+template <bool DET, bool HARD = false>
 __global__ void __launch_bounds__(256) k_loss_sample_fwd_bwd(LossSampleArgs a)
 {
     __shared__ float red[4];
@@ -226,6 +436,7 @@ __global__ void __launch_bounds__(256) k_loss_sample_fwd_bwd(LossSampleArgs a)
     __shared__ int s_np, s_nsel;
     const int b = blockIdx.x, tid = threadIdx.x;
     const int HW = a.H * a.W, half = a.span / 2;
+    int nneg = a.neg_count;
     const int nb = min(a.nbox[b], a.max_box);
     const float *bx = a.boxes + (int64_t)b * a.max_box * a.box_stride;
     // ---- positive entries: box k's window cells inside the map, in the reference's order (box, dx, dy)
@@ -274,24 +485,54 @@ __global__ void __launch_bounds__(256) k_loss_sample_fwd_bwd(LossSampleArgs a)
     }
     __syncthreads();
     const int npos = s_nsel;
-    // ---- negatives: item i keeps drawing until its cell is not a selected positive
-    for (int i = tid; i < a.neg_count; i += blockDim.x) {
-        int cell = 0;
-        for (int att = 0; att < (1 << 20); ++att) {
-            const uint32_t u = dcf_loss_rand(a.seed, b, 2, i, att);
-            cell = (int)(((uint64_t)u * (uint64_t)HW) >> 32);
-            bool hit = false;
-            for (int j = 0; j < npos; ++j) hit |= sel[j] == cell;
-            if (!hit) break;
+    if constexpr (HARD) {
+        // ---- negatives: the survivors of the selection (k_hard_compact), here put in order: key descending, then cell ascending
+        __shared__ unsigned n_key[LS_MAXNEG];
+        __shared__ int n_cell[LS_MAXNEG];
+        nneg = 0;
+        if (b >= a.hard_b0) {
+            const int32_t *ws = a.hard_ws + (int64_t)b * a.hard_stride;
+            nneg = min(min(ws[HS_K], a.neg_count), LS_MAXNEG);
+            const unsigned *keys = (const unsigned *)(ws + HS_KEYS);
+            for (int i = tid; i < nneg; i += blockDim.x) {
+                const int cell = min(max(ws[HS_LIST + i], 0), HW - 1);      // (every slot below k is filled: count(> cut) + ties taken = k)
+                n_cell[i] = cell;
+                n_key[i] = keys[cell];
+                negs[i] = cell;
+            }
+            __syncthreads();
+            for (int i = tid; i < nneg; i += blockDim.x) {
+                int rank = 0;
+                const unsigned ki = n_key[i];
+                const int ci = n_cell[i];
+                for (int j = 0; j < nneg; ++j) rank += (n_key[j] > ki || (n_key[j] == ki && n_cell[j] < ci)) ? 1 : 0;
+                negs[rank] = ci;
+            }
         }
-        negs[i] = cell;
+    } else {
+        // ---- negatives: item i keeps drawing until its cell is not a selected positive
+        for (int i = tid; i < a.neg_count; i += blockDim.x) {
+            int cell = 0;
+            for (int att = 0; att < (1 << 20); ++att) {
+                const uint32_t u = dcf_loss_rand(a.seed, b, 2, i, att);
+                cell = (int)(((uint64_t)u * (uint64_t)HW) >> 32);
+                bool hit = false;
+                for (int j = 0; j < npos; ++j) hit |= sel[j] == cell;
+                if (!hit) break;
+            }
+            negs[i] = cell;
+        }
     }
     __syncthreads();
     if (a.pos_out)
         for (int i = tid; i < a.pos_cap; i += blockDim.x) a.pos_out[(int64_t)b * a.pos_cap + i] = i < npos ? sel[i] : -1;
     if (a.neg_out)
-        for (int i = tid; i < a.neg_count; i += blockDim.x) a.neg_out[(int64_t)b * a.neg_count + i] = negs[i];
-    if (a.counts_out && tid == 0) { a.counts_out[2 * b] = npos; a.counts_out[2 * b + 1] = np; }
+        for (int i = tid; i < a.neg_count; i += blockDim.x) a.neg_out[(int64_t)b * a.neg_count + i] = i < nneg ? negs[i] : -1;
+    if (a.counts_out && tid == 0) {
+        constexpr int NC = HARD ? 3 : 2;
+        a.counts_out[NC * b] = npos; a.counts_out[NC * b + 1] = np;
+        if constexpr (HARD) a.counts_out[NC * b + 2] = nneg;
+    }
     // reduction 0 = 'last' (reference behaviour: only the last sample counts), 1 = 'sum', 2 = 'mean'
     if (a.reduction == 0 && b != a.B - 1) {
         if (DET && tid == 0) a.loss_rows[b] = 0.f;
@@ -300,7 +541,6 @@ __global__ void __launch_bounds__(256) k_loss_sample_fwd_bwd(LossSampleArgs a)
     const float wsample = a.reduction == 2 ? 1.f / (float)a.B : 1.f;
     const float *c = a.cls + b * a.cls_bs, *r = a.reg + b * a.reg_bs;
     float *gc = a.gcls + b * a.gcls_bs, *gr = a.greg + b * a.greg_bs;
-    const int nneg = a.neg_count;
     float acc = 0.f;
     const int ncls = 2 * (npos + nneg);
     for (int e = tid; e < ncls; e += blockDim.x) {
@@ -394,7 +634,7 @@ extern "C" uint32_t dcf_loss_sample_rand(uint64_t seed, int sample, int stream, 
     return dcf_loss_rand(seed, sample, stream, index, attempt);
 }
 
-static int loss_sample_impl(const char *who, float *loss_rows, const float *cls, int64_t cls_bstride, const float *reg, int64_t reg_bstride, const float *anchors,
+static int loss_sample_impl(const char *who, bool hard, void *hard_ws, float *loss_rows, const float *cls, int64_t cls_bstride, const float *reg, int64_t reg_bstride, const float *anchors,
                                        const float *boxes, const int32_t *nbox_dev, int max_box, int box_stride, int B, int H, int W,
                                        float xs, float xo, float ys, float yo, float reduced_scale, int span, int regress_type, int pos_cap,
                                        int neg_count, uint64_t seed, float reg_gain, int reduction, float *loss, float *gcls,
@@ -414,7 +654,35 @@ static int loss_sample_impl(const char *who, float *loss_rows, const float *cls,
     a.seed = seed; a.max_box = max_box; a.box_stride = box_stride; a.B = B; a.H = H; a.W = W; a.span = span;
     a.regress_type = regress_type; a.pos_cap = pos_cap; a.neg_count = neg_count; a.reduction = reduction;
     a.xs = xs; a.xo = xo; a.ys = ys; a.yo = yo; a.rs = reduced_scale; a.gain = reg_gain;
+    a.hard_ws = nullptr; a.hard_stride = 0; a.hard_b0 = 0;
     hipStream_t s = S(stream);
+    if (hard) {
+        DCF_REQUIRE(hard_ws && ((uintptr_t)hard_ws & 3) == 0, "%s: null or misaligned workspace", who);
+        DCF_REQUIRE((int64_t)H * W < (int64_t)1 << 30, "%s: map too large", who);
+        const int HW = H * W;
+        HardArgs h;
+        h.cls = cls; h.boxes = boxes; h.nbox = nbox_dev; h.cls_bs = cls_bstride; h.ws_stride = hard_ws_stride(HW); h.ws = (int32_t *)hard_ws;
+        h.max_box = max_box; h.box_stride = box_stride; h.H = H; h.W = W; h.span = span; h.neg_count = neg_count;
+        h.xs = xs; h.xo = xo; h.ys = ys; h.yo = yo; h.rs = reduced_scale;
+        h.chunk = hard_chunk(HW);
+        h.G = cdiv(HW, h.chunk);
+        // 'last' with no lists asked for: only the last sample's negatives are ever read
+        h.b0 = (reduction == 0 && !neg_out && !counts_out) ? B - 1 : 0;
+        a.hard_ws = h.ws; a.hard_stride = h.ws_stride; a.hard_b0 = h.b0;
+        const dim3 grid(h.G, B - h.b0);
+        const double map_bytes = (double)(B - h.b0) * HW * 4.0;
+        DCF_LAUNCH_B("loss_hard_keys", 5.0 * map_bytes, s, hipLaunchKernelGGL(k_hard_keys, grid, dim3(HARD_THREADS), 0, s, h));
+        for (int p = 1; p <= 3; ++p)
+            DCF_LAUNCH_B("loss_hard_pass", map_bytes, s, hipLaunchKernelGGL(k_hard_pass, grid, dim3(HARD_THREADS), 0, s, h, p));
+        DCF_LAUNCH_B("loss_hard_compact", map_bytes, s, hipLaunchKernelGGL(k_hard_compact, grid, dim3(HARD_THREADS), 0, s, h));
+        if (loss_rows) {
+            DCF_LAUNCH("loss_hard_fwd_bwd_det", s, hipLaunchKernelGGL((k_loss_sample_fwd_bwd<true, true>), dim3(B), dim3(256), 0, s, a));
+            DCF_LAUNCH("loss_rows_fold", s, hipLaunchKernelGGL(k_loss_rows_fold, dim3(1), dim3(64), 0, s, loss_rows, B, loss));
+        } else {
+            DCF_LAUNCH("loss_hard_fwd_bwd", s, hipLaunchKernelGGL((k_loss_sample_fwd_bwd<false, true>), dim3(B), dim3(256), 0, s, a));
+        }
+        return DCF_OK;
+    }
     if (loss_rows) {
         DCF_LAUNCH("loss_sample_fwd_bwd_det", s, hipLaunchKernelGGL(k_loss_sample_fwd_bwd<true>, dim3(B), dim3(256), 0, s, a));
         DCF_LAUNCH("loss_rows_fold", s, hipLaunchKernelGGL(k_loss_rows_fold, dim3(1), dim3(64), 0, s, loss_rows, B, loss));
@@ -431,7 +699,7 @@ extern "C" int dcf_loss_sample_fwd_bwd(const float *cls, int64_t cls_bstride, co
                                        int64_t gcls_bstride, float *greg, int64_t greg_bstride, int32_t *pos_out, int32_t *neg_out,
                                        int32_t *counts_out, dcf_stream_t stream)
 {
-    return loss_sample_impl("dcf_loss_sample_fwd_bwd", nullptr, cls, cls_bstride, reg, reg_bstride, anchors, boxes, nbox_dev, max_box, box_stride, B, H, W, xs,
+    return loss_sample_impl("dcf_loss_sample_fwd_bwd", false, nullptr, nullptr, cls, cls_bstride, reg, reg_bstride, anchors, boxes, nbox_dev, max_box, box_stride, B, H, W, xs,
                             xo, ys, yo, reduced_scale, span, regress_type, pos_cap, neg_count, seed, reg_gain, reduction, loss, gcls, gcls_bstride, greg,
                             greg_bstride, pos_out, neg_out, counts_out, stream);
 }
@@ -445,9 +713,41 @@ extern "C" int dcf_loss_sample_fwd_bwd_det(const float *cls, int64_t cls_bstride
                                            int32_t *counts_out, float *loss_rows, dcf_stream_t stream)
 {
     DCF_REQUIRE(loss_rows, "dcf_loss_sample_fwd_bwd_det: null loss_rows");
-    return loss_sample_impl("dcf_loss_sample_fwd_bwd_det", loss_rows, cls, cls_bstride, reg, reg_bstride, anchors, boxes, nbox_dev, max_box, box_stride, B, H,
+    return loss_sample_impl("dcf_loss_sample_fwd_bwd_det", false, nullptr, loss_rows, cls, cls_bstride, reg, reg_bstride, anchors, boxes, nbox_dev, max_box, box_stride, B, H,
                             W, xs, xo, ys, yo, reduced_scale, span, regress_type, pos_cap, neg_count, seed, reg_gain, reduction, loss, gcls, gcls_bstride,
                             greg, greg_bstride, pos_out, neg_out, counts_out, stream);
+}
+
+// loss_sampling: hard (the selection kernels above, then the device mode's positives and terms)
+extern "C" size_t dcf_loss_hard_workspace_bytes(int B, int H, int W)
+{
+    if (B <= 0 || H <= 0 || W <= 0 || (int64_t)H * W >= (int64_t)1 << 30) return 0;
+    return (size_t)B * (size_t)hard_ws_stride(H * W) * sizeof(int32_t);
+}
+
+extern "C" int dcf_loss_hard_fwd_bwd(const float *cls, int64_t cls_bstride, const float *reg, int64_t reg_bstride, const float *anchors,
+                                     const float *boxes, const int32_t *nbox_dev, int max_box, int box_stride, int B, int H, int W,
+                                     float xs, float xo, float ys, float yo, float reduced_scale, int span, int regress_type, int pos_cap,
+                                     int neg_count, uint64_t seed, float reg_gain, int reduction, float *loss, float *gcls,
+                                     int64_t gcls_bstride, float *greg, int64_t greg_bstride, int32_t *pos_out, int32_t *neg_out,
+                                     int32_t *counts_out, void *workspace, dcf_stream_t stream)
+{
+    return loss_sample_impl("dcf_loss_hard_fwd_bwd", true, workspace, nullptr, cls, cls_bstride, reg, reg_bstride, anchors, boxes, nbox_dev, max_box,
+                            box_stride, B, H, W, xs, xo, ys, yo, reduced_scale, span, regress_type, pos_cap, neg_count, seed, reg_gain, reduction, loss,
+                            gcls, gcls_bstride, greg, greg_bstride, pos_out, neg_out, counts_out, stream);
+}
+
+extern "C" int dcf_loss_hard_fwd_bwd_det(const float *cls, int64_t cls_bstride, const float *reg, int64_t reg_bstride, const float *anchors,
+                                         const float *boxes, const int32_t *nbox_dev, int max_box, int box_stride, int B, int H, int W,
+                                         float xs, float xo, float ys, float yo, float reduced_scale, int span, int regress_type, int pos_cap,
+                                         int neg_count, uint64_t seed, float reg_gain, int reduction, float *loss, float *gcls,
+                                         int64_t gcls_bstride, float *greg, int64_t greg_bstride, int32_t *pos_out, int32_t *neg_out,
+                                         int32_t *counts_out, void *workspace, float *loss_rows, dcf_stream_t stream)
+{
+    DCF_REQUIRE(loss_rows, "dcf_loss_hard_fwd_bwd_det: null loss_rows");
+    return loss_sample_impl("dcf_loss_hard_fwd_bwd_det", true, workspace, loss_rows, cls, cls_bstride, reg, reg_bstride, anchors, boxes, nbox_dev, max_box,
+                            box_stride, B, H, W, xs, xo, ys, yo, reduced_scale, span, regress_type, pos_cap, neg_count, seed, reg_gain, reduction, loss,
+                            gcls, gcls_bstride, greg, greg_bstride, pos_out, neg_out, counts_out, stream);
 }
 
 extern "C" int dcf_loss_fwd_bwd_det(const float *cls, int64_t cls_bstride, const float *reg, int64_t reg_bstride, const float *anchors,

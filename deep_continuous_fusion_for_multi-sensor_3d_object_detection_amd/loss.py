@@ -11,6 +11,11 @@ the same arithmetic as a handful of torch ops.
 subset, negatives, terms and gradients in one launch, a stateless counter hash seeded by `loss_seed` and the call count
 instead of numpy's generator) -- no host loop, no index lists over PCIe; `compat` (default) is the mode pinned to the reference.
 
+`loss_sampling: hard` is the device mode with hard negative mining: positives as in `device`, negatives = the
+`neg_sample_threshold + 1` cells outside every positive window that the head currently scores most like an object (an exact
+top-k over the score map, csrc/loss.hip k_hard_*; no randomness in the negatives).  hard_negatives() below is the host statement
+of that selection; CPU tensors take it, so the mode also runs without a device.
+
 Reference quirks are kept behind `loss_reduction: last` (default): cross-entropy on already
 soft-maxed scores (loss.py:17-20,139), 129 negatives (:125), only the last sample of the
 batch contributes (:71).  'sum' / 'mean' accumulate over the batch instead.
@@ -97,6 +102,85 @@ class _FusedLossSample(torch.autograd.Function):
         return (g * go,) + (None,) * 11
 
 
+class _FusedLossHard(torch.autograd.Function):
+    """dcf_loss_hard_fwd_bwd: the device mode's assignment with mined negatives (loss_sampling: hard); ws = the selection's workspace."""
+
+    @staticmethod
+    def forward(ctx, base, cls, reg, anc, boxes, nbox, geo, seed, gain, reduction, outs, ws, det=False):
+        from . import _hip as H
+        src = base if base is not None else cls
+        B, _, Hh, W = cls.shape
+        loss = torch.zeros(1, dtype=torch.float32, device=src.device)
+        if base is not None:
+            g = torch.zeros_like(base)
+            gcls, greg = g, g[:, 4:]
+            ctx.split = False
+        else:
+            gcls, greg = torch.zeros_like(cls), torch.zeros_like(reg)
+            g = (gcls, greg)
+            ctx.split = True
+        xs, xo, ys, yo, rs, span, rtype, pos_cap, neg_count = geo
+        args = (cls, cls.stride(0), reg, reg.stride(0), anc, boxes, nbox, boxes.shape[1], boxes.shape[2], B, Hh, W,
+                float(xs), float(xo), float(ys), float(yo), float(rs), int(span), int(rtype), int(pos_cap), int(neg_count), int(seed),
+                float(gain), int(reduction), loss, gcls, gcls.stride(0), greg, greg.stride(0),
+                None if outs is None else outs[0], None if outs is None else outs[1], None if outs is None else outs[2], ws)
+        if det:      # deterministic: true
+            H.call("dcf_loss_hard_fwd_bwd_det", *(args + (torch.empty(B, dtype=torch.float32, device=src.device), H.stream_ptr())))
+        else:
+            H.call("dcf_loss_hard_fwd_bwd", *(args + (H.stream_ptr(),)))
+        ctx.g = g
+        return loss
+
+    @staticmethod
+    def backward(ctx, go):
+        g = ctx.g
+        if ctx.split:
+            return (None, g[0] * go, g[1] * go) + (None,) * 10
+        return (g * go,) + (None,) * 12
+
+
+def _mix64(z):
+    """dcf_mix64 of csrc/loss.hip on uint64 arrays (numpy wraps modulo 2^64)."""
+    z = z + np.uint64(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def sample_rand(seed, sample, stream, index, attempt=0):
+    """dcf_loss_sample_rand for an array of indices: uint32 array (tests/test_cabi.py pins the library's function to the same hash)."""
+    idx = np.asarray(index, dtype=np.uint64)
+    ctr = np.uint64((sample << 44) | (stream << 40) | (attempt << 20)) | idx
+    with np.errstate(over="ignore"):
+        return (_mix64(np.uint64(seed & 0xFFFFFFFFFFFFFFFF) ^ _mix64(ctr)) >> np.uint64(32)).astype(np.uint32)
+
+
+def float_order(d):
+    """The order-preserving map from fp32 to uint32 (ord of `loss_sampling: hard`): flips the sign bit of a non-negative float and
+    all bits of a negative one, so unsigned comparison of the results follows the order of the floats (-0.0 below +0.0)."""
+    u = np.ascontiguousarray(d, dtype=np.float32).view(np.uint32)
+    return np.where(u & np.uint32(0x80000000), ~u, u ^ np.uint32(0x80000000)).astype(np.uint32)
+
+
+def hard_keys(cls_sample):
+    """key(cell) of one sample: cls_sample float32 [4, HW] -> uint32 [HW]; one fp32 subtraction per anchor, the worse anchor counts."""
+    c = np.ascontiguousarray(cls_sample, dtype=np.float32)
+    k = np.maximum(float_order(c[1] - c[0]), float_order(c[3] - c[2]))
+    return np.maximum(k, np.uint32(1))           # (0 marks a window cell on the device; the two keys this moves are NaN patterns)
+
+
+def hard_negatives(cls_sample, window_cells, neg_count):
+    """The host statement of the mined negative list of one sample: the candidates (cells in no positive window) ordered by key
+    descending, ties by cell ascending; the first min(neg_count, candidates) of them.  int64 array."""
+    keys = hard_keys(cls_sample)
+    cand = np.ones(keys.shape[0], dtype=bool)
+    if len(window_cells):
+        cand[np.asarray(window_cells, dtype=np.int64)] = False
+    cells = np.flatnonzero(cand)
+    order = np.lexsort((cells, -keys[cells].astype(np.int64)))
+    return cells[order[:neg_count]].astype(np.int64)
+
+
 class LossTotal(nn.Module):
     def __init__(self, config):
         super(LossTotal, self).__init__()
@@ -104,14 +188,15 @@ class LossTotal(nn.Module):
         self.regress_type = config["regress_type"]
         self.reduction = config.get("loss_reduction", "last")
         self.sampling = config.get("loss_sampling", "compat")
-        if self.sampling not in ("compat", "device"):
-            raise ValueError("loss_sampling must be compat or device (got %r)" % (self.sampling,))
+        if self.sampling not in ("compat", "device", "hard"):
+            raise ValueError("loss_sampling must be compat, device or hard (got %r)" % (self.sampling,))
         from .model import parse_deterministic_config
         self.deterministic = parse_deterministic_config(config)      # both device entries then sum in one fixed order (csrc/loss.hip, DET)
         self.seed = int(config.get("loss_seed", 0))
         self.calls = 0                     # device sampling: the call count enters the hash, so every step draws fresh lists
                                            # (saved with the checkpoint: Train.save_checkpoint / load_checkpoint)
         self.last_samples = None           # device sampling with keep_samples: (pos [B,cap], neg [B,n], counts [B,2]) of the last call
+                                           # (hard: counts [B,3] = selected positives, window entries, selected negatives; neg -1 padded)
         self.keep_samples = False
         anc = AnchorBoundingBoxFeature(config)()
         self.register_buffer("anchor_set", anc.reshape(2, 7, anc.shape[1], anc.shape[2]), persistent=False)
@@ -163,14 +248,12 @@ class LossTotal(nn.Module):
                     negatives.append([x, y])
         return positives, negatives, regress, owner
 
-    def assign_arrays(self, boxes, H, W):
-        """assign() for the hot path: the same lists as flat integer codes (cell = px * W + py) -- (positive cells, negative cells,
-        regression cells, box of each regression cell, weight of each regression cell) -- with the same consumption of numpy's
-        legacy generator: RandomState.shuffle draws the same random_interval sequence for a 1-D array of n codes as for a list
-        of n pairs (and takes its C fast path there), the negatives are drawn in the same batches.  tests/test_host_logic.py
-        pins lists and generator state to assign().  boxes: float32 ndarray [n, >= 2]."""
+    def windows(self, boxes, H, W):
+        """The positive windows of one sample, no randomness: (window entries as cell codes px * W + py in the reference's order --
+        box, dx, dy; overlapping windows give a cell twice --, regression cells, box of each, weight of each).  boxes: float32
+        ndarray [n, >= 2]."""
         c = self.config
-        rs, span, cap = c["anchor_bbox_feature"]["reduced_scale"], c["positive_range"], c["pos_sample_threshold"]
+        rs, span = c["anchor_bbox_feature"]["reduced_scale"], c["positive_range"]
         half = int(span / 2)
         f32 = np.float32
         nb = len(boxes)
@@ -196,6 +279,17 @@ class LossTotal(nn.Module):
                 rows += win
                 row_box += [k] * len(win)
                 row_w += [1.0 / (len(win) * 14)] * len(win)
+        return cells, rows, row_box, row_w
+
+    def assign_arrays(self, boxes, H, W):
+        """assign() for the hot path: the same lists as flat integer codes (cell = px * W + py) -- (positive cells, negative cells,
+        regression cells, box of each regression cell, weight of each regression cell) -- with the same consumption of numpy's
+        legacy generator: RandomState.shuffle draws the same random_interval sequence for a 1-D array of n codes as for a list
+        of n pairs (and takes its C fast path there), the negatives are drawn in the same batches.  tests/test_host_logic.py
+        pins lists and generator state to assign().  boxes: float32 ndarray [n, >= 2]."""
+        c = self.config
+        cap = c["pos_sample_threshold"]
+        cells, rows, row_box, row_w = self.windows(boxes, H, W)
         pos = np.array(cells, dtype=np.int64)
         np.random.shuffle(pos)
         pos = pos[:cap]
@@ -326,17 +420,64 @@ class LossTotal(nn.Module):
         base, cls, reg = self._head_views(cls, reg, H, W)
         geo = (self._xs, self._xo, self._ys, self._yo, c["anchor_bbox_feature"]["reduced_scale"], c["positive_range"], self.regress_type,
                c["pos_sample_threshold"], c["neg_sample_threshold"] + 1)
+        hard = self.sampling == "hard"
         outs = None
         if self.keep_samples:
             outs = (torch.empty((B, geo[7]), dtype=torch.int32, device=dev), torch.empty((B, geo[8]), dtype=torch.int32, device=dev),
-                    torch.empty((B, 2), dtype=torch.int32, device=dev))
+                    torch.empty((B, 3 if hard else 2), dtype=torch.int32, device=dev))
             self.last_samples = outs
         # rank 0 / a single process: (seed, calls) as before; other data-parallel ranks draw from streams of their own
         rank = torch.distributed.get_rank() if (torch.distributed.is_available() and torch.distributed.is_initialized()) else 0
         seed = (self.seed * 0x9E3779B1 + self.calls + rank * 0x85EBCA77C2B2AE63) & 0xFFFFFFFFFFFFFFFF
         self.calls += 1
         red = {"last": 0, "sum": 1, "mean": 2}[self.reduction]
+        if hard:
+            # the selection's workspace: allocated once per map shape, contents free between calls (all calls go onto one stream)
+            ws = getattr(self, "_hard_ws", None)
+            if ws is None or ws[0] != (B, H, W, dev):
+                from . import _hip as Hl
+                nbytes = Hl.lib().dcf_loss_hard_workspace_bytes(B, H, W)
+                ws = self._hard_ws = ((B, H, W, dev), torch.empty(max(nbytes, 4) // 4, dtype=torch.int32, device=dev))
+            return _FusedLossHard.apply(base, cls, reg, anc, boxes, nb, geo, seed, c["regress_loss_gain"], red, outs, ws[1], self.deterministic)
         return _FusedLossSample.apply(base, cls, reg, anc, boxes, nb, geo, seed, c["regress_loss_gain"], red, outs, self.deterministic)
+
+    def _forward_hard_host(self, boxes_host, nbox, cls, reg, anc, B, H, W):
+        """loss_sampling: hard on CPU tensors -- the host statement of what the device entry does: windows and positive subset with the
+        device sampler's hash (stream 1, the pos_sample_threshold smallest (key, entry) pairs, in entry order), negatives from
+        hard_negatives(), the terms through the torch path of the compat mode."""
+        c = self.config
+        cap, want = c["pos_sample_threshold"], c["neg_sample_threshold"] + 1
+        rank = torch.distributed.get_rank() if (torch.distributed.is_available() and torch.distributed.is_initialized()) else 0
+        seed = (self.seed * 0x9E3779B1 + self.calls + rank * 0x85EBCA77C2B2AE63) & 0xFFFFFFFFFFFFFFFF
+        self.calls += 1
+        bh = boxes_host.float().numpy()
+        scores = cls.detach().float().reshape(B, 4, H * W).numpy()
+        ints, floats, plan, kept = [], [], [], []
+        for b in range(B):
+            nb = min(int(nbox[b]), bh.shape[1])
+            entries, rows, row_box, row_w = self.windows(bh[b, :nb], H, W)
+            if len(entries) > cap:
+                keys = sample_rand(seed, b, 1, np.arange(len(entries)))
+                chosen = np.sort(np.lexsort((np.arange(len(entries)), keys))[:cap])
+                pos = [entries[i] for i in chosen.tolist()]
+            else:
+                pos = list(entries)
+            neg = hard_negatives(scores[b], entries, want).tolist()
+            kept.append((pos, neg, len(entries)))
+            o, of = len(ints), len(floats)
+            ints += pos + neg + rows + row_box
+            floats += row_w + bh[b, :nb, :7].reshape(-1).tolist()
+            plan.append((o, len(pos), len(neg), len(rows), of, nb))
+        if self.keep_samples:
+            pos_t, neg_t = torch.full((B, cap), -1, dtype=torch.int32), torch.full((B, want), -1, dtype=torch.int32)
+            counts = torch.zeros((B, 3), dtype=torch.int32)
+            for b, (pos, neg, n_entries) in enumerate(kept):
+                pos_t[b, :len(pos)] = torch.tensor(pos, dtype=torch.int32)
+                neg_t[b, :len(neg)] = torch.tensor(neg, dtype=torch.int32)
+                counts[b] = torch.tensor([len(pos), n_entries, len(neg)], dtype=torch.int32)
+            self.last_samples = (pos_t, neg_t, counts)
+        di, df = self._stage(ints, floats, cls.device)
+        return self._terms_host(cls, reg, anc, di, df, plan, B, H, W)
 
     def forward(self, reference_bboxes_batch, num_ref_bbox_batch, predicted_class_feature_batch, predicted_regress_feature_batch):
         cls, reg = predicted_class_feature_batch, predicted_regress_feature_batch
@@ -346,12 +487,14 @@ class LossTotal(nn.Module):
         if getattr(self, "_anc_dev", None) is None or self._anc_dev.device != dev:
             self._anc_dev = self.anchor_set.to(dev).reshape(2, 7, H * W)
         anc = self._anc_dev
-        if self.sampling == "device":
+        if self.sampling == "device" or (self.sampling == "hard" and dev.type == "cuda"):
             if dev.type != "cuda":
                 raise RuntimeError("loss_sampling: device needs CUDA tensors (the host path is loss_sampling: compat)")
             return self._forward_device_sampling(reference_bboxes_batch, num_ref_bbox_batch, cls, reg, anc, B, H, W)
         # pass CPU boxes (what a DataLoader yields) to avoid a device round trip
         boxes_host = reference_bboxes_batch.detach().cpu() if reference_bboxes_batch.is_cuda else reference_bboxes_batch.detach()
+        if self.sampling == "hard":
+            return self._forward_hard_host(boxes_host, num_ref_bbox_batch, cls, reg, anc, B, H, W)
         if dev.type == "cuda":
             return self._forward_hip_arrays(cls, reg, anc, boxes_host, num_ref_bbox_batch, B, H, W)
         # ---- host: target assignment for every sample, packed into flat lists
@@ -371,7 +514,11 @@ class LossTotal(nn.Module):
             floats += row_w + boxes_host[b, :nb, :7].reshape(-1).tolist()
             plan.append((o, len(pos), len(neg), len(rows), of, nb))
         di, df = self._stage(ints, floats, dev)
-        # ---- device: gathers + CE + Smooth-L1, vectorised per sample
+        return self._terms_host(cls, reg, anc, di, df, plan, B, H, W)
+
+    def _terms_host(self, cls, reg, anc, di, df, plan, B, H, W):
+        """The terms on the staged lists as torch ops (CPU tensors): gathers + CE + Smooth-L1, vectorised per sample."""
+        dev = cls.device
         total = torch.zeros(1, device=dev)
         acc = torch.zeros(1, device=dev)
         for b in range(B):
@@ -380,10 +527,14 @@ class LossTotal(nn.Module):
             lc = torch.zeros(1, device=dev)
             for a in range(2):                                   # per anchor: loss.py:64-65
                 sc = cls[b, 2 * a:2 * a + 2].reshape(2, H * W)
-                term = F.cross_entropy(sc[:, neg_i].t(), torch.zeros(nneg, dtype=torch.long, device=dev))
+                term = None                                      # (an empty list has no term: hard mining with no candidate cell)
+                if nneg > 0:
+                    term = F.cross_entropy(sc[:, neg_i].t(), torch.zeros(nneg, dtype=torch.long, device=dev))
                 if npos > 0:
-                    term = F.cross_entropy(sc[:, pos_i].t(), torch.ones(npos, dtype=torch.long, device=dev)) + term
-                lc = lc + term
+                    tp = F.cross_entropy(sc[:, pos_i].t(), torch.ones(npos, dtype=torch.long, device=dev))
+                    term = tp if term is None else tp + term
+                if term is not None:
+                    lc = lc + term
             lr = torch.zeros(1, device=dev)
             if nrow > 0:
                 rows = di[o + npos + nneg:o + npos + nneg + nrow]

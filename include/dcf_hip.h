@@ -539,6 +539,32 @@ int dcf_loss_sample_fwd_bwd(const float *cls, int64_t cls_bstride, const float *
                             int64_t gcls_bstride, float *greg, int64_t greg_bstride, int32_t *pos_out, int32_t *neg_out,
                             int32_t *counts_out, dcf_stream_t stream);
 
+/* (version 203) Hard negative mining (`loss_sampling: hard`): dcf_loss_sample_fwd_bwd with the negatives MINED
+ * instead of drawn.  Windows, the positive subset (same hash streams, same seed) and all terms are those of the entry above; the
+ * negatives of a sample are the min(neg_count, candidates) cells outside EVERY window entry (also those the pos_cap cut dropped)
+ * with the highest key, ties by the lower cell index, listed in that order:
+ *     key(cell) = max(1, max over anchors a of ord(fl32(cls[2a+1][cell] - cls[2a][cell]))),
+ *     ord(d) = bits(d) ^ 0x80000000 when the sign bit is clear, ~bits(d) otherwise        (unsigned; follows the order of the floats)
+ * No randomness, no duplicates, no gradient through the selection; with no candidate the negative term is absent.  An exact radix
+ * select (8-bit digits, per-workgroup histograms, integer atomics only) spread over the map, then one workgroup per sample for the
+ * terms.  workspace: dcf_loss_hard_workspace_bytes(B, H, W) bytes, 4-byte aligned, contents free on entry; calls that share it must
+ * be ordered on one stream.  reduction 0 with neg_out == counts_out == NULL mines the last sample only.
+ * Outputs for inspection: pos_out as above, neg_out int32 [B][neg_count] (-1 in unused slots), counts_out [B][3] = {selected
+ * positives, window entries, selected negatives}.  Limits as above; the _det entry sums in one fixed order (loss_rows: B floats). */
+size_t dcf_loss_hard_workspace_bytes(int B, int H, int W);
+int dcf_loss_hard_fwd_bwd(const float *cls, int64_t cls_bstride, const float *reg, int64_t reg_bstride, const float *anchors,
+                          const float *boxes, const int32_t *nbox_dev, int max_box, int box_stride, int B, int H, int W,
+                          float xs, float xo, float ys, float yo, float reduced_scale, int span, int regress_type, int pos_cap,
+                          int neg_count, uint64_t seed, float reg_gain, int reduction, float *loss, float *gcls,
+                          int64_t gcls_bstride, float *greg, int64_t greg_bstride, int32_t *pos_out, int32_t *neg_out,
+                          int32_t *counts_out, void *workspace, dcf_stream_t stream);
+int dcf_loss_hard_fwd_bwd_det(const float *cls, int64_t cls_bstride, const float *reg, int64_t reg_bstride, const float *anchors,
+                              const float *boxes, const int32_t *nbox_dev, int max_box, int box_stride, int B, int H, int W,
+                              float xs, float xo, float ys, float yo, float reduced_scale, int span, int regress_type, int pos_cap,
+                              int neg_count, uint64_t seed, float reg_gain, int reduction, float *loss, float *gcls,
+                              int64_t gcls_bstride, float *greg, int64_t greg_bstride, int32_t *pos_out, int32_t *neg_out,
+                              int32_t *counts_out, void *workspace, float *loss_rows, dcf_stream_t stream);
+
 /* ------------------------------------------------- evaluation post-processing
  * What /root/reference/test.py:88-206 does on the host, box by box.
  * dcf_eval_score_filter: test.py:88-108.  pred [B][32][h][w] fp32 (the model output: scores in channels 2a+1, decoded boxes in
