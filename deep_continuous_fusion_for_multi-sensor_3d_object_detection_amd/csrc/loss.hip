@@ -9,25 +9,18 @@
 
 namespace {
 
+// the sum of v over a workgroup of NWAVES waves (4 or 16), in a fixed order
+template <int NWAVES>
 __device__ __forceinline__ float block_sum(float v, float *red)
 {
     v = wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-// the same for a 1024-thread workgroup (16 waves), in a fixed order
-__device__ __forceinline__ float block_sum16(float v, float *red)
-{
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
+    if constexpr (NWAVES == 4) return (red[0] + red[1]) + (red[2] + red[3]);
     float t = 0.f;
 #pragma unroll
-    for (int q = 0; q < 4; ++q) t += (red[4 * q] + red[4 * q + 1]) + (red[4 * q + 2] + red[4 * q + 3]);
+    for (int q = 0; q < NWAVES / 4; ++q) t += (red[4 * q] + red[4 * q + 1]) + (red[4 * q + 2] + red[4 * q + 3]);
     return t;
 }
 
@@ -45,13 +38,144 @@ __device__ __forceinline__ float reg_target(const float *bx, const float *an, in
 }
 __device__ __forceinline__ float sl1_grad(float d) { return fabsf(d) < 1.f ? d : (d > 0.f ? 1.f : -1.f); }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The terms of one sample, written once for both kernels of this file.  The kernels differ only in where a list item comes from,
+// so each hands the code below an accessor (ListItems / SampledItems, beside their kernels) that answers
+//   npos, nneg, cell(j)     the classification list: item j < npos is a positive, the others are negatives
+//   nrows, row_cell(r), row_counts(r), row_weight(r), row_box(r)     the regression rows (a row that does not count has no term)
+//
 // DET (deterministic: true): a cell can occur several times in a sample's lists (overlapping positive windows,
 // negatives drawn with replacement), and three or more float atomics onto one address do not commute.  There the FIRST entry of a
 // cell adds the terms of all entries of that cell in list order and stores the sum once; the sample's loss value goes to its own
 // slot of loss_rows (k_loss_rows_fold adds the slots in sample order).  The lists hold a few hundred entries: the scans are cheap.
+struct SampleMaps {
+    const float *c, *r, *anc;       // the sample's scores [4][HW] and offsets [14][HW]; the anchors [2][7][HW]
+    float *gc, *gr;                 // the sample's gradient maps
+    int HW;
+    float gain, wsample;
+};
 
+// reduction 0 = 'last' (reference behaviour: only the last sample counts), 1 = 'sum', 2 = 'mean'
+__device__ __forceinline__ float sample_weight(int reduction, int B) { return reduction == 2 ? 1.f / (float)B : 1.f; }
+
+// false for a sample that 'last' leaves out: its workgroup has nothing more to do
+template <bool DET>
+__device__ __forceinline__ bool sample_counts(int reduction, int b, int B, float *loss_rows)
+{
+    if (reduction != 0 || b == B - 1) return true;
+    if constexpr (DET) {
+        // DCF-DET-BEGIN
+        if (threadIdx.x == 0) loss_rows[b] = 0.f;
+        // DCF-DET-END
+    }
+    return false;
+}
+
+// 2-way cross-entropy, entry e = (anchor a, list item): mean per list (loss.py:129-142)
+template <bool DET, class Items>
+__device__ __forceinline__ void cls_entry(const Items &L, const SampleMaps &m, int e, float &acc)
+{
+    const int npos = L.npos, nneg = L.nneg, HW = m.HW;
+    const int a = e / (npos + nneg), it = e - a * (npos + nneg);
+    const bool is_pos = it < npos;
+    const int cell = L.cell(it);
+    const float inv = 1.f / (float)(is_pos ? npos : nneg);
+    const float s0 = m.c[(int64_t)(2 * a) * HW + cell], s1 = m.c[(int64_t)(2 * a + 1) * HW + cell];
+    const float mx = fmaxf(s0, s1);
+    const float e0 = expf(s0 - mx), e1 = expf(s1 - mx);
+    const float lse = mx + logf(e0 + e1);
+    const float p0 = e0 / (e0 + e1), p1 = e1 / (e0 + e1);
+    acc += (lse - (is_pos ? s1 : s0)) * inv;
+    if constexpr (DET) {
+        // DCF-DET-BEGIN
+        const int nl = npos + nneg;
+        bool first = true;
+        for (int j = 0; j < it && first; ++j) first = L.cell(j) != cell;
+        if (first) {
+            float g0 = 0.f, g1 = 0.f;
+            for (int j = it; j < nl; ++j) {
+                if (L.cell(j) != cell) continue;
+                const bool jp = j < npos;
+                const float gj = (1.f / (float)(jp ? npos : nneg)) * m.wsample;
+                g0 += (p0 - (jp ? 0.f : 1.f)) * gj;
+                g1 += (p1 - (jp ? 1.f : 0.f)) * gj;
+            }
+            m.gc[(int64_t)(2 * a) * HW + cell] += g0;
+            m.gc[(int64_t)(2 * a + 1) * HW + cell] += g1;
+        }
+        // DCF-DET-END
+    } else {
+        const float g = inv * m.wsample;
+        atomicAdd(m.gc + (int64_t)(2 * a) * HW + cell, (p0 - (is_pos ? 0.f : 1.f)) * g);
+        atomicAdd(m.gc + (int64_t)(2 * a + 1) * HW + cell, (p1 - (is_pos ? 1.f : 0.f)) * g);
+    }
+}
+
+// Smooth-L1 of the encoded box offsets, entry e = (row, anchor a, component j) (loss.py:144-186)
+template <bool DET, class Items>
+__device__ __forceinline__ void reg_entry(const Items &L, const SampleMaps &m, int e, float &accr)
+{
+    const int row = e / 14, q = e - row * 14;
+    if (!L.row_counts(row)) return;
+    const int a = q / 7, j = q - a * 7, HW = m.HW;
+    const int cell = L.row_cell(row);
+    const float wrow = L.row_weight(row);
+    const float *an = m.anc + (int64_t)a * 7 * HW + cell;     // an[j * HW]
+    const float t = reg_target(L.row_box(row), an, j, HW);
+    const float d = m.r[(int64_t)q * HW + cell] - t;
+    const float ad = fabsf(d);
+    accr += (ad < 1.f ? 0.5f * d * d : ad - 0.5f) * wrow;
+    if constexpr (DET) {
+        // DCF-DET-BEGIN
+        bool first = true;
+        for (int r2 = 0; r2 < row && first; ++r2) first = !(L.row_cell(r2) == cell && L.row_counts(r2));
+        if (first) {
+            float gs = 0.f;
+            for (int r2 = row; r2 < L.nrows; ++r2) {
+                if (L.row_cell(r2) != cell || !L.row_counts(r2)) continue;
+                const float d2 = m.r[(int64_t)q * HW + cell] - reg_target(L.row_box(r2), an, j, HW);
+                gs += sl1_grad(d2) * L.row_weight(r2) * m.gain * m.wsample;
+            }
+            m.gr[(int64_t)q * HW + cell] += gs;
+        }
+        // DCF-DET-END
+    } else {
+        atomicAdd(m.gr + (int64_t)q * HW + cell, (ad < 1.f ? d : (d > 0.f ? 1.f : -1.f)) * wrow * m.gain * m.wsample);
+    }
+}
+
+// every entry of sample b over the workgroup's NWAVES waves, then the sample's value
+template <bool DET, int NWAVES, class Items>
+__device__ __forceinline__ void sample_terms(const Items &L, const SampleMaps &m, int b, float *red, float *loss, float *loss_rows)
+{
+    float acc = 0.f, accr = 0.f;
+    for (int e = threadIdx.x; e < 2 * (L.npos + L.nneg); e += blockDim.x) cls_entry<DET>(L, m, e, acc);
+    for (int e = threadIdx.x; e < L.nrows * 14; e += blockDim.x) reg_entry<DET>(L, m, e, accr);
+    const float tot = block_sum<NWAVES>(acc + m.gain * accr, red);
+    if constexpr (DET) {
+        // DCF-DET-BEGIN
+        if (threadIdx.x == 0) loss_rows[b] = tot * m.wsample;
+        // DCF-DET-END
+    } else {
+        if (threadIdx.x == 0) atomicAdd(loss, tot * m.wsample);
+    }
+}
+
+// The lists of the host's target assignment:
 // ints  = [B x {off_int, npos, nneg, nrow, off_float, nbox}] then per sample: pos cells, neg cells, reg cells, box of each reg cell
 // floats = per sample: weight of each reg cell, then nbox x 7 box parameters
+struct ListItems {
+    const int64_t *pos, *neg, *rows, *rbox;
+    const float *wrow, *boxes;
+    const int *lcell, *lrow;        // DET: the cells of the two lists staged in LDS (the scans read them often), or null
+    int npos, nneg, nrows;
+    __device__ __forceinline__ int cell(int j) const { return lcell ? lcell[j] : (int)(j < npos ? pos[j] : neg[j - npos]); }
+    __device__ __forceinline__ int row_cell(int r) const { return lrow ? lrow[r] : (int)rows[r]; }
+    __device__ __forceinline__ bool row_counts(int) const { return true; }
+    __device__ __forceinline__ float row_weight(int r) const { return wrow[r]; }
+    __device__ __forceinline__ const float *row_box(int r) const { return boxes + (int64_t)rbox[r] * 7; }
+};
+
 // (1024 threads: with the reference's 'last' reduction ONE workgroup does all the work, and its entries are chains of dependent
 // loads -- list item -> cell -> scores -> atomics; at 256 threads the launch took 40 us between forward and backward)
 template <bool DET>
@@ -61,110 +185,31 @@ __global__ void __launch_bounds__(1024) k_loss_fwd_bwd(const float *cls, int64_t
 {
     __shared__ float red[16];
     const int b = blockIdx.x;
-    // reduction 0 = 'last' (reference behaviour: only the last sample counts), 1 = 'sum', 2 = 'mean'
-    if (reduction == 0 && b != B - 1) {
-        if (DET && threadIdx.x == 0) loss_rows[b] = 0.f;
-        return;
-    }
-    const float wsample = reduction == 2 ? 1.f / (float)B : 1.f;
+    if (!sample_counts<DET>(reduction, b, B, loss_rows)) return;
     const int64_t *pl = ints + 6 * b;
-    const int o = (int)pl[0], npos = (int)pl[1], nneg = (int)pl[2], nrow = (int)pl[3], of = (int)pl[4];
-    const int64_t *pos = ints + o, *neg = pos + npos, *rows = neg + nneg, *rbox = rows + nrow;
-    const float *wrow = floats + of, *boxes = wrow + nrow;
-    const float *c = cls + b * cls_bs, *r = reg + b * reg_bs;
-    float *gc = gcls + b * gcls_bs, *gr = greg + b * greg_bs;
-    float acc = 0.f;
-    const int *lcell = nullptr, *lrow = nullptr;      // DET: the cells of the two lists staged in LDS (the scans below read them often)
+    const int o = (int)pl[0], of = (int)pl[4];
+    ListItems L;
+    L.npos = (int)pl[1]; L.nneg = (int)pl[2]; L.nrows = (int)pl[3];
+    L.pos = ints + o; L.neg = L.pos + L.npos; L.rows = L.neg + L.nneg; L.rbox = L.rows + L.nrows;
+    L.wrow = floats + of; L.boxes = L.wrow + L.nrows;
+    L.lcell = nullptr; L.lrow = nullptr;
     if constexpr (DET) {
         // DCF-DET-BEGIN
-        constexpr int MAXL = 2048;
+        constexpr int MAXL = 2048;      // longer lists are scanned in global memory
         __shared__ int s_cell[MAXL], s_row[MAXL];
-        if (npos + nneg <= MAXL) {
-            for (int i = threadIdx.x; i < npos + nneg; i += blockDim.x) s_cell[i] = (int)(i < npos ? pos[i] : neg[i - npos]);
-            lcell = s_cell;
+        if (L.npos + L.nneg <= MAXL) {
+            for (int i = threadIdx.x; i < L.npos + L.nneg; i += blockDim.x) s_cell[i] = L.cell(i);
+            L.lcell = s_cell;
         }
-        if (nrow <= MAXL) {
-            for (int i = threadIdx.x; i < nrow; i += blockDim.x) s_row[i] = (int)rows[i];
-            lrow = s_row;
+        if (L.nrows <= MAXL) {
+            for (int i = threadIdx.x; i < L.nrows; i += blockDim.x) s_row[i] = L.row_cell(i);
+            L.lrow = s_row;
         }
         __syncthreads();
         // DCF-DET-END
     }
-    // ---- classification: entry e = (anchor a, list item)
-    const int ncls = 2 * (npos + nneg);
-    for (int e = threadIdx.x; e < ncls; e += blockDim.x) {
-        const int a = e / (npos + nneg), it = e - a * (npos + nneg);
-        const bool is_pos = it < npos;
-        const int cell = (int)(is_pos ? pos[it] : neg[it - npos]);
-        const float inv = 1.f / (float)(is_pos ? npos : nneg);
-        const float s0 = c[(int64_t)(2 * a) * HW + cell], s1 = c[(int64_t)(2 * a + 1) * HW + cell];
-        const float m = fmaxf(s0, s1);
-        const float e0 = expf(s0 - m), e1 = expf(s1 - m);
-        const float lse = m + logf(e0 + e1);
-        const float p0 = e0 / (e0 + e1), p1 = e1 / (e0 + e1);
-        acc += (lse - (is_pos ? s1 : s0)) * inv;
-        const float g = inv * wsample;
-        if constexpr (DET) {
-            // DCF-DET-BEGIN
-            const int nl = npos + nneg;
-            auto cell_at = [&](int j) { return lcell ? lcell[j] : (int)(j < npos ? pos[j] : neg[j - npos]); };
-            bool first = true;
-            for (int j = 0; j < it && first; ++j) first = cell_at(j) != cell;
-            if (first) {
-                float g0 = 0.f, g1 = 0.f;
-                for (int j = it; j < nl; ++j) {
-                    if (cell_at(j) != cell) continue;
-                    const bool jp = j < npos;
-                    const float gj = (1.f / (float)(jp ? npos : nneg)) * wsample;
-                    g0 += (p0 - (jp ? 0.f : 1.f)) * gj;
-                    g1 += (p1 - (jp ? 1.f : 0.f)) * gj;
-                }
-                gc[(int64_t)(2 * a) * HW + cell] += g0;
-                gc[(int64_t)(2 * a + 1) * HW + cell] += g1;
-            }
-            // DCF-DET-END
-        } else {
-            atomicAdd(gc + (int64_t)(2 * a) * HW + cell, (p0 - (is_pos ? 0.f : 1.f)) * g);
-            atomicAdd(gc + (int64_t)(2 * a + 1) * HW + cell, (p1 - (is_pos ? 1.f : 0.f)) * g);
-        }
-    }
-    // ---- regression: entry e = (row, anchor a, component j)
-    float accr = 0.f;
-    for (int e = threadIdx.x; e < nrow * 14; e += blockDim.x) {
-        const int row = e / 14, q = e - row * 14;
-        const int a = q / 7, j = q - a * 7;
-        const int cell = (int)rows[row];
-        const float *bx = boxes + (int64_t)rbox[row] * 7;
-        const float *an = anc + (int64_t)a * 7 * HW + cell;     // an[j * HW]
-        const float t = reg_target(bx, an, j, HW);
-        const float d = r[(int64_t)q * HW + cell] - t;
-        const float ad = fabsf(d);
-        accr += (ad < 1.f ? 0.5f * d * d : ad - 0.5f) * wrow[row];
-        if constexpr (DET) {
-            // DCF-DET-BEGIN
-            auto row_cell = [&](int r2) { return lrow ? lrow[r2] : (int)rows[r2]; };
-            bool first = true;
-            for (int r2 = 0; r2 < row && first; ++r2) first = row_cell(r2) != cell;
-            if (first) {
-                float gs = 0.f;
-                for (int r2 = row; r2 < nrow; ++r2) {
-                    if (row_cell(r2) != cell) continue;
-                    const float d2 = r[(int64_t)q * HW + cell] - reg_target(boxes + (int64_t)rbox[r2] * 7, an, j, HW);
-                    gs += sl1_grad(d2) * wrow[r2] * gain * wsample;
-                }
-                gr[(int64_t)q * HW + cell] += gs;
-            }
-            // DCF-DET-END
-        } else {
-            atomicAdd(gr + (int64_t)q * HW + cell, (ad < 1.f ? d : (d > 0.f ? 1.f : -1.f)) * wrow[row] * gain * wsample);
-        }
-    }
-    const float tot = block_sum16(acc + gain * accr, red);
-    if constexpr (DET) {
-        if (threadIdx.x == 0) loss_rows[b] = tot * wsample;
-    } else {
-        if (threadIdx.x == 0) atomicAdd(loss, tot * wsample);
-    }
+    const SampleMaps m = {cls + b * cls_bs, reg + b * reg_bs, anc, gcls + b * gcls_bs, greg + b * greg_bs, HW, gain, sample_weight(reduction, B)};
+    sample_terms<DET, 16>(L, m, b, red, loss, loss_rows);
 }
 
 // *loss += rows[0] + rows[1] + ... in sample order
@@ -423,6 +468,26 @@ struct LossSampleArgs {
     int hard_b0;
 };
 
+// The lists the sample kernel leaves in LDS: selected positives, negatives, and the window entries as regression rows -- every entry
+// (regress_type 0) or the centre cell only; a box's rows share its weight 1 / (rows * 14)
+struct SampledItems {
+    const int *sel, *negs, *e_cell;
+    const short *e_box;
+    const int *box_first, *box_cx, *box_cy;
+    const float *bx;                // the sample's boxes, box_stride apart
+    int box_stride, regress_type, W;
+    int npos, nneg, nrows;
+    __device__ __forceinline__ int cell(int j) const { return j < npos ? sel[j] : negs[j - npos]; }
+    __device__ __forceinline__ int row_cell(int r) const { return e_cell[r]; }
+    __device__ __forceinline__ bool row_counts(int r) const { return regress_type == 0 || e_cell[r] == box_cx[e_box[r]] * W + box_cy[e_box[r]]; }
+    __device__ __forceinline__ float row_weight(int r) const
+    {
+        const int k = e_box[r];
+        return 1.f / (float)((regress_type != 0 ? 1 : box_first[k + 1] - box_first[k]) * 14);
+    }
+    __device__ __forceinline__ const float *row_box(int r) const { return bx + (int64_t)e_box[r] * box_stride; }
+};
+
 template <bool DET, bool HARD = false>
 __global__ void __launch_bounds__(256) k_loss_sample_fwd_bwd(LossSampleArgs a)
 {
@@ -533,98 +598,11 @@ __global__ void __launch_bounds__(256) k_loss_sample_fwd_bwd(LossSampleArgs a)
         a.counts_out[NC * b] = npos; a.counts_out[NC * b + 1] = np;
         if constexpr (HARD) a.counts_out[NC * b + 2] = nneg;
     }
-    // reduction 0 = 'last' (reference behaviour: only the last sample counts), 1 = 'sum', 2 = 'mean'
-    if (a.reduction == 0 && b != a.B - 1) {
-        if (DET && tid == 0) a.loss_rows[b] = 0.f;
-        return;
-    }
-    const float wsample = a.reduction == 2 ? 1.f / (float)a.B : 1.f;
-    const float *c = a.cls + b * a.cls_bs, *r = a.reg + b * a.reg_bs;
-    float *gc = a.gcls + b * a.gcls_bs, *gr = a.greg + b * a.greg_bs;
-    float acc = 0.f;
-    const int ncls = 2 * (npos + nneg);
-    for (int e = tid; e < ncls; e += blockDim.x) {
-        const int an = e / (npos + nneg), it = e - an * (npos + nneg);
-        const bool is_pos = it < npos;
-        const int cell = is_pos ? sel[it] : negs[it - npos];
-        const float inv = 1.f / (float)(is_pos ? npos : nneg);
-        const float s0 = c[(int64_t)(2 * an) * HW + cell], s1 = c[(int64_t)(2 * an + 1) * HW + cell];
-        const float m = fmaxf(s0, s1);
-        const float e0 = expf(s0 - m), e1 = expf(s1 - m);
-        const float lse = m + logf(e0 + e1);
-        const float p0 = e0 / (e0 + e1), p1 = e1 / (e0 + e1);
-        acc += (lse - (is_pos ? s1 : s0)) * inv;
-        const float g = inv * wsample;
-        if constexpr (DET) {
-            // DCF-DET-BEGIN
-            const int nl = npos + nneg;
-            auto cell_at = [&](int j) { return j < npos ? sel[j] : negs[j - npos]; };
-            bool first = true;
-            for (int j = 0; j < it && first; ++j) first = cell_at(j) != cell;
-            if (first) {
-                float g0 = 0.f, g1 = 0.f;
-                for (int j = it; j < nl; ++j) {
-                    if (cell_at(j) != cell) continue;
-                    const bool jp = j < npos;
-                    const float gj = (1.f / (float)(jp ? npos : nneg)) * wsample;
-                    g0 += (p0 - (jp ? 0.f : 1.f)) * gj;
-                    g1 += (p1 - (jp ? 1.f : 0.f)) * gj;
-                }
-                gc[(int64_t)(2 * an) * HW + cell] += g0;
-                gc[(int64_t)(2 * an + 1) * HW + cell] += g1;
-            }
-            // DCF-DET-END
-        } else {
-            atomicAdd(gc + (int64_t)(2 * an) * HW + cell, (p0 - (is_pos ? 0.f : 1.f)) * g);
-            atomicAdd(gc + (int64_t)(2 * an + 1) * HW + cell, (p1 - (is_pos ? 1.f : 0.f)) * g);
-        }
-    }
-    // ---- regression rows: every window entry (regress_type 0) or the centre cell only; a box's rows share its weight 1 / (rows * 14)
-    float accr = 0.f;
-    for (int e = tid; e < np * 14; e += blockDim.x) {
-        const int row = e / 14, q = e - row * 14;
-        const int k = e_box[row], cell = e_cell[row];
-        int nrows_k = box_first[k + 1] - box_first[k];
-        if (a.regress_type != 0) {
-            if (cell != box_cx[k] * a.W + box_cy[k]) continue;
-            nrows_k = 1;
-        }
-        const float wrow = 1.f / (float)(nrows_k * 14);
-        const int an_ = q / 7, j = q - an_ * 7;
-        const float *bk = bx + (int64_t)k * a.box_stride;
-        const float *an = a.anc + (int64_t)an_ * 7 * HW + cell;
-        const float t = reg_target(bk, an, j, HW);
-        const float d = r[(int64_t)q * HW + cell] - t;
-        const float ad = fabsf(d);
-        accr += (ad < 1.f ? 0.5f * d * d : ad - 0.5f) * wrow;
-        if constexpr (DET) {
-            // DCF-DET-BEGIN
-            // (a row counts when every window entry regresses, or when it is its box's centre cell)
-            auto active = [&](int r2) { return a.regress_type == 0 || e_cell[r2] == box_cx[e_box[r2]] * a.W + box_cy[e_box[r2]]; };
-            bool first = true;
-            for (int r2 = 0; r2 < row && first; ++r2) first = !(e_cell[r2] == cell && active(r2));
-            if (first) {
-                float gs = 0.f;
-                for (int r2 = row; r2 < np; ++r2) {
-                    if (e_cell[r2] != cell || !active(r2)) continue;
-                    const int k2 = e_box[r2];
-                    const float w2 = 1.f / (float)((a.regress_type != 0 ? 1 : box_first[k2 + 1] - box_first[k2]) * 14);
-                    const float d2 = r[(int64_t)q * HW + cell] - reg_target(bx + (int64_t)k2 * a.box_stride, an, j, HW);
-                    gs += sl1_grad(d2) * w2 * a.gain * wsample;
-                }
-                gr[(int64_t)q * HW + cell] += gs;
-            }
-            // DCF-DET-END
-        } else {
-            atomicAdd(gr + (int64_t)q * HW + cell, (ad < 1.f ? d : (d > 0.f ? 1.f : -1.f)) * wrow * a.gain * wsample);
-        }
-    }
-    const float tot = block_sum(acc + a.gain * accr, red);
-    if constexpr (DET) {
-        if (tid == 0) a.loss_rows[b] = tot * wsample;
-    } else {
-        if (tid == 0) atomicAdd(a.loss, tot * wsample);
-    }
+    if (!sample_counts<DET>(a.reduction, b, a.B, a.loss_rows)) return;
+    const SampledItems L = {sel, negs, e_cell, e_box, box_first, box_cx, box_cy, bx, a.box_stride, a.regress_type, a.W, npos, nneg, np};
+    const SampleMaps m = {a.cls + b * a.cls_bs, a.reg + b * a.reg_bs, a.anc, a.gcls + b * a.gcls_bs, a.greg + b * a.greg_bs, HW, a.gain,
+                          sample_weight(a.reduction, a.B)};
+    sample_terms<DET, 4>(L, m, b, red, a.loss, a.loss_rows);
 }
 
 }  // namespace

@@ -28,115 +28,54 @@ import torch.nn.functional as F
 from .model import AnchorBoundingBoxFeature
 
 
+REDUCTION = {"last": 0, "sum": 1, "mean": 2}       # the kernels' reduction codes (csrc/loss.hip)
+
+
 class _FusedLoss(torch.autograd.Function):
-    """loss = dcf_loss_fwd_bwd(head outputs, staged targets); the same launch leaves dL/d(head outputs) in dense maps,
-    which backward hands to autograd scaled by the incoming gradient.  With `base` = the [B,32,h,w] head tensor that
-    cls / reg are views of, the gradient goes straight to it (no slice-backward kernels)."""
+    """loss = one launch of csrc/loss.hip on the head outputs; the same launch leaves dL/d(head outputs) in dense maps, which
+    backward hands to autograd scaled by the incoming gradient.  With `base` = the [B,32,h,w] head tensor that cls / reg are views
+    of, the gradient goes straight to it (no slice-backward kernels).  launch(loss, gcls, greg) makes the library call: the list-driven
+    entry or one of the sampled ones, with whatever else that entry takes."""
 
     @staticmethod
-    def forward(ctx, base, cls, reg, anc, di, df, B, HW, gain, reduction, det=False):
-        from . import _hip as H
-        src = base if base is not None else cls
-        loss = torch.zeros(1, dtype=torch.float32, device=src.device)
+    def forward(ctx, base, cls, reg, launch):
+        loss = torch.zeros(1, dtype=torch.float32, device=cls.device)
         if base is not None:
             g = torch.zeros_like(base)
-            gb = g.stride(0)
             gcls, greg = g, g[:, 4:]
-            ctx.split = False
         else:
-            gcls, greg = torch.zeros_like(cls), torch.zeros_like(reg)
-            g = (gcls, greg)
-            gb = None
-            ctx.split = True
-        if det:      # deterministic: true -- duplicate cells summed in list order, the samples' values added in sample order
-            H.call("dcf_loss_fwd_bwd_det", cls, cls.stride(0), reg, reg.stride(0), anc, di, df, B, HW, float(gain), int(reduction), loss,
-                   gcls, gcls.stride(0), greg, greg.stride(0), torch.empty(B, dtype=torch.float32, device=src.device), H.stream_ptr())
-        else:
-            H.call("dcf_loss_fwd_bwd", cls, cls.stride(0), reg, reg.stride(0), anc, di, df, B, HW, float(gain), int(reduction), loss,
-                   gcls, gcls.stride(0), greg, greg.stride(0), H.stream_ptr())
-        ctx.g = g
+            g = gcls, greg = torch.zeros_like(cls), torch.zeros_like(reg)
+        launch(loss, gcls, greg)
+        ctx.g, ctx.split = g, base is None
         return loss
 
     @staticmethod
     def backward(ctx, go):
         g = ctx.g
         if ctx.split:
-            return None, g[0] * go, g[1] * go, None, None, None, None, None, None, None, None
-        return g * go, None, None, None, None, None, None, None, None, None, None
+            return None, g[0] * go, g[1] * go, None
+        return g * go, None, None, None
 
 
-class _FusedLossSample(torch.autograd.Function):
-    """dcf_loss_sample_fwd_bwd: target assignment + loss + gradients in one launch (loss_sampling: device)."""
-
-    @staticmethod
-    def forward(ctx, base, cls, reg, anc, boxes, nbox, geo, seed, gain, reduction, outs, det=False):
-        from . import _hip as H
-        src = base if base is not None else cls
-        B, _, Hh, W = cls.shape
-        loss = torch.zeros(1, dtype=torch.float32, device=src.device)
-        if base is not None:
-            g = torch.zeros_like(base)
-            gcls, greg = g, g[:, 4:]
-            ctx.split = False
-        else:
-            gcls, greg = torch.zeros_like(cls), torch.zeros_like(reg)
-            g = (gcls, greg)
-            ctx.split = True
-        xs, xo, ys, yo, rs, span, rtype, pos_cap, neg_count = geo
-        args = (cls, cls.stride(0), reg, reg.stride(0), anc, boxes, nbox, boxes.shape[1], boxes.shape[2], B, Hh, W,
-                float(xs), float(xo), float(ys), float(yo), float(rs), int(span), int(rtype), int(pos_cap), int(neg_count), int(seed),
-                float(gain), int(reduction), loss, gcls, gcls.stride(0), greg, greg.stride(0),
-                None if outs is None else outs[0], None if outs is None else outs[1], None if outs is None else outs[2])
-        if det:      # deterministic: true
-            H.call("dcf_loss_sample_fwd_bwd_det", *(args + (torch.empty(B, dtype=torch.float32, device=src.device), H.stream_ptr())))
-        else:
-            H.call("dcf_loss_sample_fwd_bwd", *(args + (H.stream_ptr(),)))
-        ctx.g = g
-        return loss
-
-    @staticmethod
-    def backward(ctx, go):
-        g = ctx.g
-        if ctx.split:
-            return (None, g[0] * go, g[1] * go) + (None,) * 9
-        return (g * go,) + (None,) * 11
-
-
-class _FusedLossHard(torch.autograd.Function):
-    """dcf_loss_hard_fwd_bwd: the device mode's assignment with mined negatives (loss_sampling: hard); ws = the selection's workspace."""
-
-    @staticmethod
-    def forward(ctx, base, cls, reg, anc, boxes, nbox, geo, seed, gain, reduction, outs, ws, det=False):
-        from . import _hip as H
-        src = base if base is not None else cls
-        B, _, Hh, W = cls.shape
-        loss = torch.zeros(1, dtype=torch.float32, device=src.device)
-        if base is not None:
-            g = torch.zeros_like(base)
-            gcls, greg = g, g[:, 4:]
-            ctx.split = False
-        else:
-            gcls, greg = torch.zeros_like(cls), torch.zeros_like(reg)
-            g = (gcls, greg)
-            ctx.split = True
-        xs, xo, ys, yo, rs, span, rtype, pos_cap, neg_count = geo
-        args = (cls, cls.stride(0), reg, reg.stride(0), anc, boxes, nbox, boxes.shape[1], boxes.shape[2], B, Hh, W,
-                float(xs), float(xo), float(ys), float(yo), float(rs), int(span), int(rtype), int(pos_cap), int(neg_count), int(seed),
-                float(gain), int(reduction), loss, gcls, gcls.stride(0), greg, greg.stride(0),
-                None if outs is None else outs[0], None if outs is None else outs[1], None if outs is None else outs[2], ws)
-        if det:      # deterministic: true
-            H.call("dcf_loss_hard_fwd_bwd_det", *(args + (torch.empty(B, dtype=torch.float32, device=src.device), H.stream_ptr())))
-        else:
-            H.call("dcf_loss_hard_fwd_bwd", *(args + (H.stream_ptr(),)))
-        ctx.g = g
-        return loss
-
-    @staticmethod
-    def backward(ctx, go):
-        g = ctx.g
-        if ctx.split:
-            return (None, g[0] * go, g[1] * go) + (None,) * 10
-        return (g * go,) + (None,) * 12
+def pack_lists(samples):
+    """The layout dcf_loss_fwd_bwd reads, from per-sample (pos, neg, rows, row_box, row_w, boxes[:, :7]) -- arrays or lists:
+    ints (int64)    = B x {off_int, npos, nneg, nrow, off_float, nbox}, then per sample: positive, negative, regression cells, box
+                      of each regression cell;
+    floats (float32) = per sample: weight of each regression cell, then nbox x 7 box parameters.
+    Offsets count from the start of each buffer."""
+    B = len(samples)
+    head = np.empty((B, 6), np.int64)
+    parts_i, parts_f = [head.reshape(-1)], []
+    o, of = 6 * B, 0
+    for b, (pos, neg, rows, row_box, row_w, boxes) in enumerate(samples):
+        pos, neg, rows, row_box = [np.asarray(v, dtype=np.int64) for v in (pos, neg, rows, row_box)]
+        row_w, bx = np.asarray(row_w, dtype=np.float32), np.asarray(boxes, dtype=np.float32).reshape(-1)
+        head[b] = (o, pos.size, neg.size, rows.size, of, bx.size // 7)
+        parts_i += [pos, neg, rows, row_box]
+        parts_f += [row_w, bx]
+        o += pos.size + neg.size + 2 * rows.size
+        of += row_w.size + bx.size
+    return np.concatenate(parts_i), np.concatenate(parts_f) if parts_f else np.zeros(0, np.float32)
 
 
 def _mix64(z):
@@ -304,11 +243,21 @@ class LossTotal(nn.Module):
         return pos, np.array(neg, dtype=np.int64), np.array(rows, dtype=np.int64), np.array(row_box, dtype=np.int64), np.array(row_w, dtype=np.float32)
 
     # ------------------------------------------------------------------ device-side terms
-    def _stage_arrays(self, ints, floats, dev):
-        """_stage for numpy arrays (the CUDA path): straight into pinned buffers.  A ring of three buffer pairs: the one being
-        refilled was last used three steps ago, so the wait for its copies never blocks -- with a single pair the host stalled
-        here every step until the GPU had reached the previous step's loss (the host enqueues a step about as fast as the GPU
-        runs it, so that wait set the pace)."""
+    def _step_seed(self):
+        """The seed of this call's hash streams, and the call counted.  Rank 0 / a single process: (seed, calls); other
+        data-parallel ranks draw from streams of their own."""
+        rank = torch.distributed.get_rank() if (torch.distributed.is_available() and torch.distributed.is_initialized()) else 0
+        seed = (self.seed * 0x9E3779B1 + self.calls + rank * 0x85EBCA77C2B2AE63) & 0xFFFFFFFFFFFFFFFF
+        self.calls += 1
+        return seed
+
+    def _stage(self, ints, floats, dev):
+        """The packed lists (numpy) as tensors on dev.  CUDA: through pinned buffers, all index lists / boxes of the step in two
+        async copies.  A ring of three buffer pairs: the one being refilled was last used three steps ago, so the wait for its
+        copies never blocks -- with a single pair the host stalled here every step until the GPU had reached the previous step's
+        loss (the host enqueues a step about as fast as the GPU runs it, so that wait set the pace)."""
+        if dev.type != "cuda":
+            return torch.from_numpy(ints), torch.from_numpy(floats)
         ni, nf = max(ints.size, 1), max(floats.size, 1)
         ring = getattr(self, "_stage_ring", None)
         if ring is None or ring[0][0].numel() < ni or ring[0][1].numel() < nf:
@@ -329,57 +278,41 @@ class LossTotal(nn.Module):
         st[2].record()
         return di, df
 
-    def _stage(self, ints, floats, dev):
-        """One pinned staging buffer per kind: all index lists / boxes of the step go up in two async copies,
-        so the host never waits for the device while it builds the loss."""
-        if dev.type != "cuda":
-            return torch.tensor(ints, dtype=torch.long), torch.tensor(floats, dtype=torch.float32)
-        ni, nf = max(len(ints), 1), max(len(floats), 1)
-        st = getattr(self, "_stage_buf", None)
-        if st is None or st[0].numel() < ni or st[1].numel() < nf:
-            st = [torch.empty(max(ni, 1 << 16), dtype=torch.long).pin_memory(), torch.empty(max(nf, 1 << 12), dtype=torch.float32).pin_memory(), None]
-            self._stage_buf = st
-        if st[2] is not None:
-            st[2].synchronize()          # the previous step's copies have long completed
-        st[0][:len(ints)] = torch.tensor(ints, dtype=torch.long)
-        st[1][:len(floats)] = torch.tensor(floats, dtype=torch.float32)
-        di = st[0][:ni].to(dev, non_blocking=True)
-        df = st[1][:nf].to(dev, non_blocking=True)
-        st[2] = torch.cuda.Event()
-        st[2].record()
-        return di, df
+    def _forward_lists(self, cls, reg, anc, samples, B, H, W):
+        """The terms on per-sample lists (pack_lists): one launch of dcf_loss_fwd_bwd for CUDA tensors, torch ops for CPU tensors."""
+        di, df = self._stage(*pack_lists(samples), cls.device)
+        if cls.device.type != "cuda":
+            return self._terms_host(cls, reg, anc, di, df, B, H, W)
+        from . import _hip as Hl
+        base, cls, reg = self._head_views(cls, reg, H, W)
+        gain, red = float(self.config["regress_loss_gain"]), REDUCTION[self.reduction]
+
+        def launch(loss, gcls, greg):
+            args = (cls, cls.stride(0), reg, reg.stride(0), anc, di, df, B, H * W, gain, red, loss, gcls, gcls.stride(0), greg, greg.stride(0))
+            if self.deterministic:   # duplicate cells summed in list order, the samples' values added in sample order
+                Hl.call("dcf_loss_fwd_bwd_det", *args, torch.empty(B, dtype=torch.float32, device=cls.device), Hl.stream_ptr())
+            else:
+                Hl.call("dcf_loss_fwd_bwd", *args, Hl.stream_ptr())
+        return _FusedLoss.apply(base, cls, reg, launch)
 
     def _forward_hip(self, cls, reg, anc, ints, floats, plan, B, H, W):
-        """Device half as one launch: the per-sample table goes in front of the index lists (one staging copy)."""
-        head = []
+        """Device half as one launch on explicit lists: plan = per sample (off_int, npos, nneg, nrow, off_float, nbox), offsets into
+        ints (positive, negative, regression cells, box of each regression cell) and floats (weights, nbox x 7 box parameters)."""
+        ints, floats = np.asarray(ints, dtype=np.int64), np.asarray(floats, dtype=np.float32)
+        samples = []
         for (o, npos, nneg, nrow, of, nb) in plan:
-            head += [o + 6 * B, npos, nneg, nrow, of, nb]
-        di, df = self._stage(head + ints, floats, cls.device)
-        HW = H * W
-        base, cls, reg = self._head_views(cls, reg, H, W)
-        red = {"last": 0, "sum": 1, "mean": 2}[self.reduction]
-        return _FusedLoss.apply(base, cls, reg, anc, di, df, B, HW, self.config["regress_loss_gain"], red, self.deterministic)
+            cuts = np.cumsum([o, npos, nneg, nrow, nrow])
+            samples.append(tuple(ints[i:j] for i, j in zip(cuts[:-1], cuts[1:])) + (floats[of:of + nrow], floats[of + nrow:of + nrow + 7 * nb]))
+        return self._forward_lists(cls, reg, anc, samples, B, H, W)
 
     def _forward_hip_arrays(self, cls, reg, anc, boxes_host, nbox, B, H, W):
-        """The CUDA path of the compat mode: numpy target assignment (assign_arrays) packed as dcf_loss_fwd_bwd wants it
-        (per-sample table, then per sample: positive, negative, regression cells, box of each regression cell | weights, boxes)."""
+        """The CUDA path of the compat mode: numpy target assignment (assign_arrays), no Python lists of cells."""
         bh = boxes_host.numpy() if boxes_host.dtype == torch.float32 else boxes_host.float().numpy()
-        head = np.empty((B, 6), np.int64)
-        parts_i, parts_f = [], []
-        o, of = 6 * B, 0
+        samples = []
         for b in range(B):
             nb = int(nbox[b])
-            pos, neg, rows, row_box, row_w = self.assign_arrays(bh[b, :nb], H, W)
-            head[b] = (o, pos.size, neg.size, rows.size, of, nb)
-            parts_i += [pos, neg, rows, row_box]
-            bx = bh[b, :nb, :7].reshape(-1)
-            parts_f += [row_w, bx]
-            o += pos.size + neg.size + 2 * rows.size
-            of += row_w.size + bx.size
-        di, df = self._stage_arrays(np.concatenate([head.reshape(-1)] + parts_i), np.concatenate(parts_f) if parts_f else np.zeros(0, np.float32), cls.device)
-        base, cls, reg = self._head_views(cls, reg, H, W)
-        red = {"last": 0, "sum": 1, "mean": 2}[self.reduction]
-        return _FusedLoss.apply(base, cls, reg, anc, di, df, B, H * W, self.config["regress_loss_gain"], red, self.deterministic)
+            samples.append(self.assign_arrays(bh[b, :nb], H, W) + (bh[b, :nb, :7],))
+        return self._forward_lists(cls, reg, anc, samples, B, H, W)
 
     @staticmethod
     def _head_views(cls, reg, H, W):
@@ -418,28 +351,33 @@ class LossTotal(nn.Module):
             boxes = boxes.float().contiguous()
         nb = nbox.to(device=dev, dtype=torch.int32, non_blocking=True) if torch.is_tensor(nbox) else torch.tensor([int(v) for v in nbox], dtype=torch.int32, device=dev)
         base, cls, reg = self._head_views(cls, reg, H, W)
-        geo = (self._xs, self._xo, self._ys, self._yo, c["anchor_bbox_feature"]["reduced_scale"], c["positive_range"], self.regress_type,
-               c["pos_sample_threshold"], c["neg_sample_threshold"] + 1)
+        span, pos_cap, neg_count = c["positive_range"], c["pos_sample_threshold"], c["neg_sample_threshold"] + 1
+        rs, gain, red = c["anchor_bbox_feature"]["reduced_scale"], c["regress_loss_gain"], REDUCTION[self.reduction]
         hard = self.sampling == "hard"
-        outs = None
+        outs = (None, None, None)
         if self.keep_samples:
-            outs = (torch.empty((B, geo[7]), dtype=torch.int32, device=dev), torch.empty((B, geo[8]), dtype=torch.int32, device=dev),
+            outs = (torch.empty((B, pos_cap), dtype=torch.int32, device=dev), torch.empty((B, neg_count), dtype=torch.int32, device=dev),
                     torch.empty((B, 3 if hard else 2), dtype=torch.int32, device=dev))
             self.last_samples = outs
-        # rank 0 / a single process: (seed, calls) as before; other data-parallel ranks draw from streams of their own
-        rank = torch.distributed.get_rank() if (torch.distributed.is_available() and torch.distributed.is_initialized()) else 0
-        seed = (self.seed * 0x9E3779B1 + self.calls + rank * 0x85EBCA77C2B2AE63) & 0xFFFFFFFFFFFFFFFF
-        self.calls += 1
-        red = {"last": 0, "sum": 1, "mean": 2}[self.reduction]
+        seed = self._step_seed()
+        from . import _hip as Hl
+        tail = ()
         if hard:
             # the selection's workspace: allocated once per map shape, contents free between calls (all calls go onto one stream)
             ws = getattr(self, "_hard_ws", None)
             if ws is None or ws[0] != (B, H, W, dev):
-                from . import _hip as Hl
                 nbytes = Hl.lib().dcf_loss_hard_workspace_bytes(B, H, W)
                 ws = self._hard_ws = ((B, H, W, dev), torch.empty(max(nbytes, 4) // 4, dtype=torch.int32, device=dev))
-            return _FusedLossHard.apply(base, cls, reg, anc, boxes, nb, geo, seed, c["regress_loss_gain"], red, outs, ws[1], self.deterministic)
-        return _FusedLossSample.apply(base, cls, reg, anc, boxes, nb, geo, seed, c["regress_loss_gain"], red, outs, self.deterministic)
+            tail = (ws[1],)
+        name = ("dcf_loss_hard_fwd_bwd" if hard else "dcf_loss_sample_fwd_bwd") + ("_det" if self.deterministic else "")
+
+        def launch(loss, gcls, greg):
+            rows = (torch.empty(B, dtype=torch.float32, device=dev),) if self.deterministic else ()
+            Hl.call(name, cls, cls.stride(0), reg, reg.stride(0), anc, boxes, nb, boxes.shape[1], boxes.shape[2], B, H, W,
+                    float(self._xs), float(self._xo), float(self._ys), float(self._yo), float(rs), int(span), int(self.regress_type),
+                    int(pos_cap), int(neg_count), int(seed), float(gain), red, loss, gcls, gcls.stride(0), greg, greg.stride(0),
+                    *outs, *tail, *rows, Hl.stream_ptr())
+        return _FusedLoss.apply(base, cls, reg, launch)
 
     def _forward_hard_host(self, boxes_host, nbox, cls, reg, anc, B, H, W):
         """loss_sampling: hard on CPU tensors -- the host statement of what the device entry does: windows and positive subset with the
@@ -447,12 +385,10 @@ class LossTotal(nn.Module):
         hard_negatives(), the terms through the torch path of the compat mode."""
         c = self.config
         cap, want = c["pos_sample_threshold"], c["neg_sample_threshold"] + 1
-        rank = torch.distributed.get_rank() if (torch.distributed.is_available() and torch.distributed.is_initialized()) else 0
-        seed = (self.seed * 0x9E3779B1 + self.calls + rank * 0x85EBCA77C2B2AE63) & 0xFFFFFFFFFFFFFFFF
-        self.calls += 1
+        seed = self._step_seed()
         bh = boxes_host.float().numpy()
         scores = cls.detach().float().reshape(B, 4, H * W).numpy()
-        ints, floats, plan, kept = [], [], [], []
+        samples, kept = [], []
         for b in range(B):
             nb = min(int(nbox[b]), bh.shape[1])
             entries, rows, row_box, row_w = self.windows(bh[b, :nb], H, W)
@@ -464,10 +400,7 @@ class LossTotal(nn.Module):
                 pos = list(entries)
             neg = hard_negatives(scores[b], entries, want).tolist()
             kept.append((pos, neg, len(entries)))
-            o, of = len(ints), len(floats)
-            ints += pos + neg + rows + row_box
-            floats += row_w + bh[b, :nb, :7].reshape(-1).tolist()
-            plan.append((o, len(pos), len(neg), len(rows), of, nb))
+            samples.append((pos, neg, rows, row_box, row_w, bh[b, :nb, :7]))
         if self.keep_samples:
             pos_t, neg_t = torch.full((B, cap), -1, dtype=torch.int32), torch.full((B, want), -1, dtype=torch.int32)
             counts = torch.zeros((B, 3), dtype=torch.int32)
@@ -476,8 +409,7 @@ class LossTotal(nn.Module):
                 neg_t[b, :len(neg)] = torch.tensor(neg, dtype=torch.int32)
                 counts[b] = torch.tensor([len(pos), n_entries, len(neg)], dtype=torch.int32)
             self.last_samples = (pos_t, neg_t, counts)
-        di, df = self._stage(ints, floats, cls.device)
-        return self._terms_host(cls, reg, anc, di, df, plan, B, H, W)
+        return self._forward_lists(cls, reg, anc, samples, B, H, W)
 
     def forward(self, reference_bboxes_batch, num_ref_bbox_batch, predicted_class_feature_batch, predicted_regress_feature_batch):
         cls, reg = predicted_class_feature_batch, predicted_regress_feature_batch
@@ -497,8 +429,8 @@ class LossTotal(nn.Module):
             return self._forward_hard_host(boxes_host, num_ref_bbox_batch, cls, reg, anc, B, H, W)
         if dev.type == "cuda":
             return self._forward_hip_arrays(cls, reg, anc, boxes_host, num_ref_bbox_batch, B, H, W)
-        # ---- host: target assignment for every sample, packed into flat lists
-        ints, floats, plan = [], [], []
+        # ---- host: target assignment for every sample (assign(): the reference's lists and its order of generator draws)
+        samples = []
         for b in range(B):
             nb = int(num_ref_bbox_batch[b])
             pos, neg, regress, owner = self.assign(boxes_host[b, :nb], H, W)
@@ -508,17 +440,13 @@ class LossTotal(nn.Module):
                     rows.append(regress[m][0] * W + regress[m][1])
                     row_box.append(k)
                     row_w.append(1.0 / (len(owner[k]) * 14))
-            o = len(ints)
-            ints += [p[0] * W + p[1] for p in pos] + [q[0] * W + q[1] for q in neg] + rows + row_box
-            of = len(floats)
-            floats += row_w + boxes_host[b, :nb, :7].reshape(-1).tolist()
-            plan.append((o, len(pos), len(neg), len(rows), of, nb))
-        di, df = self._stage(ints, floats, dev)
-        return self._terms_host(cls, reg, anc, di, df, plan, B, H, W)
+            samples.append(([p[0] * W + p[1] for p in pos], [q[0] * W + q[1] for q in neg], rows, row_box, row_w, boxes_host[b, :nb, :7].numpy()))
+        return self._forward_lists(cls, reg, anc, samples, B, H, W)
 
-    def _terms_host(self, cls, reg, anc, di, df, plan, B, H, W):
-        """The terms on the staged lists as torch ops (CPU tensors): gathers + CE + Smooth-L1, vectorised per sample."""
+    def _terms_host(self, cls, reg, anc, di, df, B, H, W):
+        """The terms on the packed lists as torch ops (CPU tensors): gathers + CE + Smooth-L1, vectorised per sample."""
         dev = cls.device
+        plan = di[:6 * B].reshape(B, 6).tolist()
         total = torch.zeros(1, device=dev)
         acc = torch.zeros(1, device=dev)
         for b in range(B):

@@ -539,7 +539,7 @@ int dcf_loss_sample_fwd_bwd(const float *cls, int64_t cls_bstride, const float *
                             int64_t gcls_bstride, float *greg, int64_t greg_bstride, int32_t *pos_out, int32_t *neg_out,
                             int32_t *counts_out, dcf_stream_t stream);
 
-/* (version 203) Hard negative mining (`loss_sampling: hard`): dcf_loss_sample_fwd_bwd with the negatives MINED
+/* (version 202 still: added without a new minor) Hard negative mining (`loss_sampling: hard`): dcf_loss_sample_fwd_bwd with the negatives MINED
  * instead of drawn.  Windows, the positive subset (same hash streams, same seed) and all terms are those of the entry above; the
  * negatives of a sample are the min(neg_count, candidates) cells outside EVERY window entry (also those the pos_cap cut dropped)
  * with the highest key, ties by the lower cell index, listed in that order:

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+from _loss_util import assign_lists, flat_lists
 from _util import M64, from_dev, golden_cfg, load_golden, pkg, q, rnd, to_dev
 from oracle import loss_ref, model_ref
 from test_gpu_loss_sampling import _setup, sampler_statement
@@ -106,19 +107,7 @@ def _assign_lists(cfg, boxes, nb, pos_neg=None):
     """Per sample the five lists of oracle/loss_ref.py::loss_from_lists from LossTotal.assign (host side, numpy's generator as it
     stands); pos_neg: take the positive and negative cells from there instead (the device sampler's).  Weights as fp32, the way
     the kernels hold them."""
-    Lc = pkg("loss").LossTotal(dict(cfg, loss_sampling="compat"))
-    lists, bxs = [], []
-    for b in range(boxes.shape[0]):
-        n = int(nb[b])
-        pos, neg, regress, owner = Lc.assign(boxes[b, :n], H, W)
-        rows, row_box, row_w = [], [], []
-        for k in range(n):
-            for m in owner[k]:
-                rows.append(regress[m][0] * W + regress[m][1]); row_box.append(k); row_w.append(1.0 / (len(owner[k]) * 14))
-        pos, neg = ([p[0] * W + p[1] for p in pos], [v[0] * W + v[1] for v in neg]) if pos_neg is None else pos_neg[b]
-        lists.append((pos, neg, rows, row_box, np.asarray(row_w, dtype=np.float32)))
-        bxs.append(boxes[b, :n, :7].numpy())
-    return lists, bxs
+    return assign_lists(pkg("loss").LossTotal(dict(cfg, loss_sampling="compat")), boxes, nb, H, W, pos_neg)[:2]
 
 
 # ------------------------------------------------------------------------------------------------------------------ list kernel
@@ -212,13 +201,7 @@ def test_hand_built_lists_long_and_repeated(deterministic):
     boxes, nb = _boxes()
     L = pkg("loss").LossTotal(cfg).cuda()
     assert L.deterministic == deterministic
-    ints, floats, plan = [], [], []
-    for b, (pos, neg, rows, row_box, row_w) in enumerate(lists):
-        n = int(nb[b])
-        o, of = len(ints), len(floats)
-        ints += pos + neg + rows + row_box
-        floats += [float(v) for v in row_w] + boxes[b, :n, :7].reshape(-1).tolist()
-        plan.append((o, len(pos), len(neg), len(rows), of, n))
+    ints, floats, plan = flat_lists(lists, [boxes[b, :int(nb[b]), :7].numpy() for b in range(B)])
     c1, r1 = cls.cuda().requires_grad_(True), reg.cuda().requires_grad_(True)
     loss = L._forward_hip(c1, r1, L.anchor_set.reshape(2, 7, H * W), ints, floats, plan, B, H, W)
     loss.backward()

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from _loss_util import assign_lists
 from _util import M64, golden_cfg, load_golden, pkg
 from test_gpu_loss_sampling import _setup, sampler_statement
 
@@ -70,37 +71,26 @@ _SHARED = {}
 
 
 def _shared(name):
-    """Per map, computed once: config, labels, window entries per sample, the regression rows of the list-driven kernel, the positive
+    """Per map, computed once: config, labels, window entries per sample, the positive
     lists `loss_sampling: device` returns for the same seed, and the regression head input."""
     if name in _SHARED:
         return _SHARED[name]
     cfg, boxes, nb, H, W = _case(name)
     Lm = pkg("loss")
     Lh = Lm.LossTotal(cfg)
-    Lc = Lm.LossTotal(dict(cfg, loss_sampling="compat"))
-    windows, rows = [], []
-    for b in range(B):
-        n = int(nb[b])
-        windows.append(Lh.windows(boxes[b, :n].numpy(), H, W)[0])
-        np.random.seed(0)
-        _, _, regress, owner = Lc.assign(boxes[b, :n], H, W)
-        rr, rb, rw = [], [], []
-        for k in range(n):
-            for m in owner[k]:
-                rr.append(regress[m][0] * W + regress[m][1]); rb.append(k); rw.append(1.0 / (len(owner[k]) * 14))
-        rows.append((rr, rb, rw))
+    windows = [Lh.windows(boxes[b, :int(nb[b])].numpy(), H, W)[0] for b in range(B)]
     reg = torch.rand(B, 14, H, W, generator=torch.Generator().manual_seed(9)) - 0.5
     Ld = Lm.LossTotal(dict(cfg, loss_sampling="device")).cuda()
     Ld.keep_samples = True
     Ld(boxes, nb, torch.rand(B, 4, H, W).cuda(), reg.cuda())
     dev_pos, _, dev_counts = [t.cpu().numpy() for t in Ld.last_samples]
-    _SHARED[name] = (cfg, boxes, nb, H, W, windows, rows, reg, dev_pos, dev_counts)
+    _SHARED[name] = (cfg, boxes, nb, H, W, windows, reg, dev_pos, dev_counts)
     return _SHARED[name]
 
 
 def _statement(name, cls, call=0):
     """(pos, neg, window entries) per sample from the host statement."""
-    cfg, boxes, nb, H, W, windows, rows, reg, dev_pos, dev_counts = _shared(name)
+    cfg, boxes, nb, H, W, windows, reg, dev_pos, dev_counts = _shared(name)
     Lm = pkg("loss")
     L = Lm.LossTotal(cfg)
     seed = (cfg["loss_seed"] * 0x9E3779B1 + call) & M64
@@ -115,17 +105,9 @@ def _statement(name, cls, call=0):
 
 def _list_kernel(name, cls, lists, reduction="mean", deterministic=False):
     """dcf_loss_fwd_bwd on the given lists: (loss, dL/dcls, dL/dreg)."""
-    cfg, boxes, nb, H, W, windows, rows, reg, dev_pos, dev_counts = _shared(name)
+    cfg, boxes, nb, H, W, windows, reg, dev_pos, dev_counts = _shared(name)
     Lc = pkg("loss").LossTotal(dict(cfg, loss_sampling="compat", loss_reduction=reduction, deterministic=deterministic)).cuda()
-    ints, floats, plan = [], [], []
-    for b in range(B):
-        n = int(nb[b])
-        pos, neg, _ = lists[b]
-        rr, rb, rw = rows[b]
-        o, of = len(ints), len(floats)
-        ints += pos + neg + rr + rb
-        floats += rw + boxes[b, :n, :7].reshape(-1).tolist()
-        plan.append((o, len(pos), len(neg), len(rr), of, n))
+    ints, floats, plan = assign_lists(Lc, boxes, nb, H, W, lists)[2]
     c2, r2 = cls.cuda().requires_grad_(True), reg.cuda().requires_grad_(True)
     anc = Lc.anchor_set.cuda().reshape(2, 7, H * W)
     ref = Lc._forward_hip(c2, r2, anc, ints, floats, plan, B, H, W)
@@ -134,7 +116,7 @@ def _list_kernel(name, cls, lists, reduction="mean", deterministic=False):
 
 
 def _run_hard(name, cls, keep=True, boxes_dev=False, L=None, **over):
-    cfg, boxes, nb, H, W, windows, rows, reg, dev_pos, dev_counts = _shared(name)
+    cfg, boxes, nb, H, W, windows, reg, dev_pos, dev_counts = _shared(name)
     if L is None:
         L = pkg("loss").LossTotal(dict(cfg, **over)).cuda()
     L.keep_samples = keep
@@ -153,7 +135,7 @@ def _close(loss, gc, gr, ref):
 @pytest.mark.parametrize("pattern", PATTERNS)
 @pytest.mark.parametrize("name", list(MAPS))
 def test_hard_lists_equal_the_host_statement(name, pattern):
-    cfg, boxes, nb, H, W, windows, rows, reg, dev_pos, dev_counts = _shared(name)
+    cfg, boxes, nb, H, W, windows, reg, dev_pos, dev_counts = _shared(name)
     Lm = pkg("loss")
     cls = _scores(pattern, H, W, windows)
     L, loss, gc, gr, (pos, neg, counts) = _run_hard(name, cls)
@@ -199,7 +181,7 @@ def test_hard_lists_equal_the_host_statement(name, pattern):
 @pytest.mark.parametrize("reduction", ["last", "sum", "mean"])
 def test_hard_reductions(reduction):
     name = "64x48-3"
-    cfg, boxes, nb, H, W, windows, rows, reg, dev_pos, dev_counts = _shared(name)
+    cfg, boxes, nb, H, W, windows, reg, dev_pos, dev_counts = _shared(name)
     cls = _scores("uniform", H, W, windows, seed=1)
     want = _statement(name, cls)
     ref = _list_kernel(name, cls, want, reduction=reduction)
@@ -215,7 +197,7 @@ def test_hard_reductions(reduction):
 @pytest.mark.parametrize("pattern", ["uniform", "quantised"])
 def test_hard_deterministic_entry(pattern):
     name = "64x48-20"                                 # overlapping windows: cells repeat in the positive list
-    cfg, boxes, nb, H, W, windows, rows, reg, dev_pos, dev_counts = _shared(name)
+    cfg, boxes, nb, H, W, windows, reg, dev_pos, dev_counts = _shared(name)
     cls = _scores(pattern, H, W, windows, seed=2)
     runs = [_run_hard(name, cls, deterministic=True) for _ in range(2)]
     for a, b in zip(runs[0][1:4], runs[1][1:4]):
@@ -228,7 +210,7 @@ def test_hard_deterministic_entry(pattern):
 
 def test_hard_negatives_ignore_the_call_count_and_labels_may_live_on_the_device():
     name = "64x48-20"
-    cfg, boxes, nb, H, W, windows, rows, reg, dev_pos, dev_counts = _shared(name)
+    cfg, boxes, nb, H, W, windows, reg, dev_pos, dev_counts = _shared(name)
     cls = _scores("uniform", H, W, windows, seed=3)
     L, _, _, _, first = _run_hard(name, cls)
     _, _, _, _, second = _run_hard(name, cls, L=L)
@@ -245,7 +227,7 @@ def test_hard_rejected_shapes():
     """More than 64 boxes, or neg_count > 512, raise as they do in device mode."""
     Hm = pkg("_hip")
     name = "64x48-3"
-    cfg, boxes, nb, H, W, windows, rows, reg, dev_pos, dev_counts = _shared(name)
+    cfg, boxes, nb, H, W, windows, reg, dev_pos, dev_counts = _shared(name)
     cls = _scores("uniform", H, W, windows)
     for mode in ("hard", "device"):
         L = pkg("loss").LossTotal(dict(cfg, loss_sampling=mode, neg_sample_threshold=512)).cuda()

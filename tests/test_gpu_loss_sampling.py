@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from _loss_util import assign_lists
 from _util import M64, golden_cfg, load_golden, pkg, rand32
 
 pytestmark = pytest.mark.gpu
@@ -85,8 +86,7 @@ def test_device_sampler_lists_properties_and_loss(n_boxes):
     seed = (cfg["loss_seed"] * 0x9E3779B1 + 0) & M64
     cap, nneg = cfg["pos_sample_threshold"], cfg["neg_sample_threshold"] + 1
     span = cfg["positive_range"]
-    ints, floats, plan = [], [], []
-    Lc = Lm.LossTotal(dict(cfg, loss_sampling="compat"))
+    want = []
     for b in range(boxes.shape[0]):
         n = int(nb[b])
         want_pos, want_neg, n_entries = sampler_statement(L, boxes[b].numpy(), n, H, W, seed, b)
@@ -108,18 +108,10 @@ def test_device_sampler_lists_properties_and_loss(n_boxes):
         assert set(want_pos) <= cells
         if n_entries > cap:
             assert len(want_pos) == cap
-        # --- the same lists through the list-driven kernel
-        np.random.seed(0)
-        _, _, regress, owner = Lc.assign(boxes[b, :n], H, W)
-        rows, row_box, row_w = [], [], []
-        for k in range(n):
-            for m in owner[k]:
-                rows.append(regress[m][0] * W + regress[m][1]); row_box.append(k); row_w.append(1.0 / (len(owner[k]) * 14))
-        o = len(ints)
-        ints += want_pos + want_neg + rows + row_box
-        of = len(floats)
-        floats += row_w + boxes[b, :n, :7].reshape(-1).tolist()
-        plan.append((o, len(want_pos), len(want_neg), len(rows), of, n))
+        want.append((want_pos, want_neg))
+    # --- the same lists through the list-driven kernel
+    Lc = Lm.LossTotal(dict(cfg, loss_sampling="compat"))
+    ints, floats, plan = assign_lists(Lc, boxes, nb, H, W, want)[2]
     c2 = cls.cuda().requires_grad_(True)
     r2 = reg.cuda().requires_grad_(True)
     Lc = Lc.cuda()
@@ -130,6 +122,39 @@ def test_device_sampler_lists_properties_and_loss(n_boxes):
     assert torch.allclose(c1.grad, c2.grad, rtol=1e-5, atol=1e-7) and torch.allclose(r1.grad, r2.grad, rtol=1e-5, atol=1e-7)
     if n_boxes == 20:
         assert int(counts[0, 1]) > cap                   # the subset branch really ran
+
+
+@pytest.mark.parametrize("sampling", ["compat", "device", "hard"])
+def test_base_and_split_gradient_layouts_agree_bitwise(sampling):
+    """The same scores once as views of one contiguous [3,32,64,48] head tensor (the gradient goes straight to it) and once as two
+    separate leaves (two gradient maps), deterministic: true: the summation order is that of the lists and strides do not enter
+    the arithmetic, so loss and gradients are equal bit for bit, and the head's other channels get exactly zero."""
+    cfg, boxes, nb, _, _, H, W = _setup(20)
+    cfg = dict(cfg, loss_sampling=sampling, deterministic=True, loss_reduction="mean")
+    Lm = pkg("loss")
+    head = torch.rand(3, 32, H, W, generator=torch.Generator().manual_seed(8)) - 0.5
+    probe = Lm.LossTotal(cfg)
+    assert len(probe.windows(boxes[0, :int(nb[0])].numpy(), H, W)[0]) > cfg["pos_sample_threshold"]      # the subset branch runs
+    out = {}
+    for form in ("base", "split"):
+        L = Lm.LossTotal(cfg).cuda()                     # fresh: calls = 0 both times
+        np.random.seed(21)                               # compat draws from numpy's generator
+        if form == "base":
+            leaf = head.cuda().requires_grad_(True)
+            c, r = leaf[:, :4], leaf[:, 4:18]
+        else:
+            c, r = head[:, :4].contiguous().cuda().requires_grad_(True), head[:, 4:18].contiguous().cuda().requires_grad_(True)
+        assert (L._head_views(c, r, H, W)[0] is leaf) if form == "base" else (L._head_views(c, r, H, W)[0] is None)
+        loss = L(boxes, nb, c, r)
+        loss.backward()
+        if form == "base":
+            assert float(leaf.grad[:, 18:].abs().max()) == 0.0
+            out[form] = (loss.detach().clone(), leaf.grad[:, :4].clone(), leaf.grad[:, 4:18].clone())
+        else:
+            out[form] = (loss.detach().clone(), c.grad.clone(), r.grad.clone())
+    for a, b in zip(out["base"], out["split"]):
+        assert torch.equal(a, b)
+    assert float(out["base"][1].abs().sum()) > 0 and float(out["base"][2].abs().sum()) > 0
 
 
 def test_device_sampler_is_stateless_and_advances_per_call():

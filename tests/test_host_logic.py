@@ -228,6 +228,38 @@ def test_assign_arrays_equals_assign_lists_and_generator_state():
                 assert len(pos) == cfg["pos_sample_threshold"]
 
 
+def test_pack_lists_is_the_same_for_assign_lists_and_assign_arrays():
+    """loss.pack_lists, the one writer of dcf_loss_fwd_bwd's ints | floats layout: assign()'s lists and assign_arrays()'s arrays
+    under the same numpy seed give identical int64 / float32 buffers, and the B x 6 table in front indexes them -- on the 64 x 48
+    map of tests/test_gpu_loss_sampling.py (20 / 10 / 20 boxes, clipped windows, more window entries than pos_sample_threshold)."""
+    from _loss_util import assign_lists
+    from test_gpu_loss_sampling import _setup
+    cfg, boxes, nb, _, _, H, W = _setup(20)
+    Lm = pkg("loss")
+    L = Lm.LossTotal(dict(cfg, loss_sampling="compat"))
+    B = boxes.shape[0]
+    np.random.seed(13)
+    lists, bxs, _ = assign_lists(L, boxes, nb, H, W)
+    np.random.seed(13)
+    arrays = [L.assign_arrays(boxes[b, :int(nb[b])].numpy(), H, W) + (bxs[b],) for b in range(B)]
+    ints, floats = Lm.pack_lists([lists[b] + (bxs[b],) for b in range(B)])
+    ints_a, floats_a = Lm.pack_lists(arrays)
+    assert ints.dtype == ints_a.dtype == np.int64 and floats.dtype == floats_a.dtype == np.float32
+    assert np.array_equal(ints, ints_a) and np.array_equal(floats.view(np.uint32), floats_a.view(np.uint32))
+    assert len(lists[0][0]) == cfg["pos_sample_threshold"]                     # the subset branch ran
+    end_i, end_f = 6 * B, 0
+    for b, (o, npos, nneg, nrow, of, nbox) in enumerate(ints[:6 * B].reshape(B, 6).tolist()):
+        pos, neg, rows, row_box, row_w = lists[b]
+        assert (o, of) == (end_i, end_f)                                       # the samples follow one another without gaps
+        assert (npos, nneg, nrow, nbox) == (len(pos), len(neg), len(rows), int(nb[b])) and nneg == cfg["neg_sample_threshold"] + 1
+        assert ints[o:o + npos].tolist() == pos and ints[o + npos:o + npos + nneg].tolist() == neg
+        assert ints[o + npos + nneg:o + npos + nneg + nrow].tolist() == rows
+        assert ints[o + npos + nneg + nrow:o + npos + nneg + 2 * nrow].tolist() == row_box
+        assert np.array_equal(floats[of:of + nrow], row_w) and np.array_equal(floats[of + nrow:of + nrow + 7 * nbox], bxs[b].reshape(-1))
+        end_i, end_f = o + npos + nneg + 2 * nrow, of + nrow + 7 * nbox
+    assert (end_i, end_f) == (ints.size, floats.size)
+
+
 def test_profile_names_map_to_kernels_of_the_committed_pmc_summary():
     """bench.rocprof_kernel turns the runtime's launch names into rocprofv3's (function, template arguments); a name it maps
     wrongly silently loses its `traffic` figure, so the families of the cfg2 step are pinned to the committed summary."""
