@@ -72,6 +72,14 @@ SIGNATURES = {
     "dcf_eval_nms_workspace_bytes": (c_size_t, [c_int]),
     "dcf_eval_nms": (c_int, [P, P, c_int, c_int, ctypes.c_double, P, P, P, P]),
     "dcf_eval_match": (c_int, [P, c_int, P, c_int, P, c_int, P, P]),
+    # eval_metric: ranked (csrc/evalpost.hip, k_rank_* / k_ap_*)
+    "dcf_eval_rank_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dcf_eval_rank_filter": (c_int, [P, c_int, c_int, c_int, c_float, c_int, P, P, P, P, P, P]),
+    "dcf_eval_match_ranked_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "dcf_eval_match_ranked": (c_int, [P, P, P, c_int, P, c_int, P, c_int, P, P, P]),
+    "dcf_eval_accumulate": (c_int, [P, P, P, P, P, c_int, P, c_int, P, P, c_i64, P, P]),
+    "dcf_eval_ap_workspace_bytes": (c_size_t, [c_i64]),
+    "dcf_eval_ap": (c_int, [P, P, P, c_i64, c_int, P, P, P, P]),
     "dcf_wgrad_finalize_rows": (c_int, [P, c_int, P, P, P, P, P, P, P, c_float, P]),
     "dcf_bn_workspace_bytes": (c_size_t, [c_int]),
     "dcf_bn_train_fwd": (c_int, [c_int, P, P, P, P, P, P, P, P, P, c_i64, c_int, c_float, c_float, c_int, P, P]),

@@ -112,17 +112,32 @@ __device__ bool ev_sat(const double (*A)[2], const double (*B)[2])
     return true;
 }
 
+// evalgeom.bev_rect(c[:2], c[3:5], c[6]): counter-clockwise in (x, y)
+__device__ void ev_rect(const float *b, double (*rect)[2])
+{
+    const double cx = b[0], cy = b[1], l = b[3], w = b[4], yaw = b[6];
+    const double hl = l / 2, hw = w / 2, c = cos(yaw), s = sin(yaw);
+    const double sl[4] = {-1, 1, 1, -1}, sw[4] = {-1, -1, 1, 1};
+    for (int k = 0; k < 4; ++k) {
+        rect[k][0] = cx + sl[k] * hl * c - sw[k] * hw * s;
+        rect[k][1] = cy + sl[k] * hl * s + sw[k] * hw * c;
+    }
+}
+
+// bird's-eye IoU of two bev_rect rectangles (evalrank.bev_iou): no nudge; NaN for a zero-area pair (compares false everywhere)
+__device__ double ev_bev_iou(const double (*r1)[2], const double (*r2)[2])
+{
+    double poly[12][2];
+    const int n = ev_clip(r1, r2, poly);
+    const double ia = n >= 3 ? ev_shoelace(poly, n) : 0.0;
+    const double a1 = ev_shoelace(r1, 4), a2 = ev_shoelace(r2, 4);
+    return ia / (a1 + a2 - ia);
+}
+
 __device__ void ev_prep_one(const float *b, EvGeom &g)
 {
     const double cx = b[0], cy = b[1], cz = b[2], l = b[3], w = b[4], h = b[5], yaw = b[6];
-    {   // evalgeom.bev_rect(c[:2], c[3:5], c[6])
-        const double hl = l / 2, hw = w / 2, c = cos(yaw), s = sin(yaw);
-        const double sl[4] = {-1, 1, 1, -1}, sw[4] = {-1, -1, 1, 1};
-        for (int k = 0; k < 4; ++k) {
-            g.rect[k][0] = cx + sl[k] * hl * c - sw[k] * hw * s;
-            g.rect[k][1] = cy + sl[k] * hl * s + sw[k] * hw * c;
-        }
-    }
+    ev_rect(b, g.rect);
     double X[8], Y[8], Z[8];
     ev_corners(cx, cy, cz, l, w, h, yaw, X, Y, Z);
     const int order[4] = {3, 2, 1, 0};
@@ -169,6 +184,8 @@ __global__ void __launch_bounds__(256) k_eval_pairs(const EvGeom *geom, const in
             bool over;
             if (mode == 0) {
                 over = ev_sat(gi.rect, gj.rect);
+            } else if (mode == 2) {
+                over = ev_bev_iou(gi.rect, gj.rect) > thr;
             } else {
                 double i3, i2;
                 ev_iou(gi.foot, gi.top, gi.bot, gi.area, gi.vol, gj.footn, gj.topn, gj.botn, gj.arean, gj.voln, i3, i2);
@@ -262,6 +279,248 @@ __global__ void __launch_bounds__(1024) k_eval_score_filter(const float *pred, i
     if (threadIdx.x == 0) count[b] = base_s;          // may exceed cap: the caller checks
 }
 
+// ------------------------------------------------------------------ ranked evaluation (eval_metric: ranked)
+// Everything below is decided on integer keys and fp64 geometry (evalrank.py is the host statement).
+
+constexpr int EV_TILE = 1024;            // keys per LDS tile of the counting rank (8 KiB)
+constexpr int EV_LEVELS = 40;            // recall levels of the KITTI R40 average precision
+
+// total-order map of fp32 bits: larger float <=> larger unsigned (-0.0 below +0.0)
+__device__ __forceinline__ unsigned ev_orderable(float s)
+{
+    const unsigned u = __float_as_uint(s);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ unsigned long long ev_key(float s, unsigned index)
+{
+    return ((unsigned long long)ev_orderable(s) << 32) | (unsigned long long)(0xFFFFFFFFu - index);
+}
+
+// Keys of one sample's candidates with score > thr, compacted in candidate-index order (one workgroup per sample, as
+// k_eval_score_filter).  keys [B][2 hw]; total[b] = how many were kept, count[b] = min(total, cap).
+__global__ void __launch_bounds__(1024) k_rank_compact(const float *pred, int hw, float thr, int cap, unsigned long long *keys, int32_t *count, int32_t *total)
+{
+    __shared__ int wsum[16];
+    __shared__ int base_s;
+    const int b = blockIdx.x;
+    const float *p = pred + (size_t)b * 32 * hw;
+    unsigned long long *out = keys + (size_t)b * 2 * hw;
+    if (threadIdx.x == 0) base_s = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int c0 = 0; c0 < 2 * hw; c0 += 1024) {
+        const int c = c0 + threadIdx.x;
+        const int a = c >= hw ? 1 : 0, px = c - a * hw;
+        const float sc = c < 2 * hw ? p[(size_t)(2 * a + 1) * hw + px] : 0.0f;
+        const bool ok = c < 2 * hw && sc > thr;                  // a NaN score is never kept
+        const unsigned long long bal = __ballot(ok);
+        const int before = __popcll(bal & ((1ull << lane) - 1));
+        if (lane == 0) wsum[wave] = __popcll(bal);
+        __syncthreads();
+        int off = base_s;
+        for (int w = 0; w < wave; ++w) off += wsum[w];
+        const int pos = off + before;
+        if (ok && pos < 2 * hw) out[pos] = ev_key(sc, (unsigned)c);
+        __syncthreads();
+        if (threadIdx.x == 0) { int tot = 0; for (int w = 0; w < 16; ++w) tot += wsum[w]; base_s += tot; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { total[b] = base_s; count[b] = min(base_s, cap); }
+}
+
+// Rank by counting: the position of a candidate is the number of larger keys of its sample (keys are unique, so the positions
+// are a permutation: no sort, no scatter hazard).  Exact whatever total is; only ranks < cap are written.
+__global__ void __launch_bounds__(256) k_rank_place(const float *pred, int hw, int cap, const unsigned long long *keys, const int32_t *total, float *boxes,
+                                                    float *scores)
+{
+    __shared__ unsigned long long tile[EV_TILE];
+    const int b = blockIdx.y;
+    const int n = min(total[b], 2 * hw);
+    if ((int)(blockIdx.x * 256) >= n) return;                    // the whole workgroup leaves together
+    const unsigned long long *kb = keys + (size_t)b * 2 * hw;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long mine = i < n ? kb[i] : ~0ull;
+    int rank = 0;
+    for (int j0 = 0; j0 < n; j0 += EV_TILE) {
+        __syncthreads();
+        for (int q = threadIdx.x; q < EV_TILE; q += 256) tile[q] = j0 + q < n ? kb[j0 + q] : 0ull;   // 0 is below every key
+        __syncthreads();
+#pragma unroll 8
+        for (int q = 0; q < EV_TILE; ++q) rank += tile[q] > mine ? 1 : 0;
+    }
+    if (i >= n || rank >= cap) return;
+    const unsigned idx = 0xFFFFFFFFu - (unsigned)(mine & 0xFFFFFFFFull);
+    if (idx >= (unsigned)(2 * hw)) return;
+    const int a = idx >= (unsigned)hw ? 1 : 0, px = (int)idx - a * hw;
+    const float *p = pred + (size_t)b * 32 * hw;
+    float *ob = boxes + ((size_t)b * cap + rank) * 7;
+    for (int k = 0; k < 7; ++k) ob[k] = p[(size_t)(18 + 7 * a + k) * hw + px];
+    scores[(size_t)b * cap + rank] = p[(size_t)(2 * a + 1) * hw + px];
+}
+
+// iou[i][r] = bird's-eye IoU of candidate i (a survivor of the suppression) with labelled row r; NaN where there is no pair
+__global__ void __launch_bounds__(256) k_rank_iou(const float *boxes, const int32_t *keep, const int *count, int n_max, const float *refs, int R, double *iou)
+{
+    const int n = min(*count, n_max);
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = (int)(t / R), r = (int)(t - (long long)i * R);
+    if (i >= n) return;
+    double v = __longlong_as_double(0x7ff8000000000000ll);
+    const float *rb = refs + (size_t)r * 9;
+    if (keep[i] != 0 && rb[8] == 1.0f) {
+        double r1[4][2], r2[4][2];
+        ev_rect(boxes + (size_t)i * 7, r1);
+        ev_rect(rb, r2);
+        v = ev_bev_iou(r1, r2);
+    }
+    iou[(size_t)i * R + r] = v;
+}
+
+// One wave per IoU threshold walks the survivors in rank order: the best row not yet taken at this threshold (lanes stride over
+// the rows; IoU ties go to the lower row), a pair iff its IoU > t.  The waves meet in an LDS bit mask, written out at the end.
+__global__ void __launch_bounds__(1024) k_rank_match(const double *iou, const int32_t *keep, const int *count, int n_max, int R, const double *thr, int nthr,
+                                                     unsigned *tpmask)
+{
+    __shared__ unsigned msk[EV_CAP];
+    const int n = min(min(*count, n_max), EV_CAP);
+    for (int q = threadIdx.x; q < n; q += blockDim.x) msk[q] = 0u;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (wave < nthr) {
+        const double t = thr[wave];
+        unsigned long long taken = 0ull;                         // bit k: row lane + 64 k is taken
+        for (int i = 0; i < n; ++i) {
+            if (keep[i] == 0) continue;
+            double best = -__longlong_as_double(0x7ff0000000000000ll);
+            int bestr = 0x7fffffff;
+            for (int r = lane, k = 0; r < R; r += 64, ++k) {
+                if ((taken >> k) & 1ull) continue;
+                const double v = iou[(size_t)i * R + r];
+                if (v > best) { best = v; bestr = r; }           // NaN never wins; ascending r keeps the lower row on a tie
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const double ob = __shfl_xor(best, o, 64);
+                const int orow = __shfl_xor(bestr, o, 64);
+                if (ob > best || (ob == best && orow < bestr)) { best = ob; bestr = orow; }
+            }
+            if (best > t && bestr < R) {
+                if ((bestr & 63) == lane) taken |= 1ull << (bestr >> 6);
+                if (lane == 0) atomicOr(&msk[i], 1u << wave);
+            }
+        }
+    }
+    __syncthreads();
+    for (int q = threadIdx.x; q < n; q += blockDim.x) tpmask[q] = msk[q];
+}
+
+// Order-preserving append of one sample's survivors (score, tpmask) at the cursor; state = {cursor, n_gt, truncated samples, -}.
+// The cursor keeps counting past the capacity (the summary raises then); nothing past it is written.
+__global__ void __launch_bounds__(1024) k_rank_accumulate(const float *scores, const unsigned *tpmask, const int32_t *keep, const int *count, const int *total,
+                                                          int n_max, const float *refs, int R, float *acc_scores, unsigned *acc_tp, long long capacity,
+                                                          long long *state)
+{
+    __shared__ int wsum[16];
+    __shared__ long long base_s;
+    __shared__ int ngt_s;
+    const int n = min(*count, n_max);
+    if (threadIdx.x == 0) { base_s = state[0]; ngt_s = 0; }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int c0 = 0; c0 < n; c0 += 1024) {
+        const int i = c0 + threadIdx.x;
+        const bool ok = i < n && keep[i] != 0;
+        const unsigned long long bal = __ballot(ok);
+        const int before = __popcll(bal & ((1ull << lane) - 1));
+        if (lane == 0) wsum[wave] = __popcll(bal);
+        __syncthreads();
+        long long pos = base_s + before;
+        for (int w = 0; w < wave; ++w) pos += wsum[w];
+        if (ok && pos >= 0 && pos < capacity) { acc_scores[pos] = scores[i]; acc_tp[pos] = tpmask[i]; }
+        __syncthreads();
+        if (threadIdx.x == 0) { int tot = 0; for (int w = 0; w < 16; ++w) tot += wsum[w]; base_s += tot; }
+        __syncthreads();
+    }
+    for (int r0 = 0; r0 < R; r0 += 1024) {
+        const int r = r0 + threadIdx.x;
+        const unsigned long long bal = __ballot(r < R && refs[(size_t)r * 9 + 8] == 1.0f);
+        if (lane == 0) atomicAdd(&ngt_s, (int)__popcll(bal));
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        state[0] = base_s;
+        state[1] += ngt_s;
+        if (*total > n_max) state[2] += 1;
+    }
+}
+
+// Global rank of every accumulated detection by counting over (orderable score, ~index) keys; its tpmask goes to that rank
+__global__ void __launch_bounds__(256) k_ap_rank(const float *acc_scores, const unsigned *acc_tp, const long long *state, long long capacity, unsigned *sorted_tp)
+{
+    __shared__ unsigned long long tile[EV_TILE];
+    const int n = (int)max(0ll, min(state[0], capacity));
+    if ((int)(blockIdx.x * 256) >= n) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long mine = i < n ? ev_key(acc_scores[i], (unsigned)i) : ~0ull;
+    int rank = 0;
+    for (int j0 = 0; j0 < n; j0 += EV_TILE) {
+        __syncthreads();
+        for (int q = threadIdx.x; q < EV_TILE; q += 256) tile[q] = j0 + q < n ? ev_key(acc_scores[j0 + q], (unsigned)(j0 + q)) : 0ull;
+        __syncthreads();
+#pragma unroll 8
+        for (int q = 0; q < EV_TILE; ++q) rank += tile[q] > mine ? 1 : 0;
+    }
+    if (i < n && rank < n) sorted_tp[rank] = acc_tp[i];
+}
+
+// One workgroup per threshold: c_k by a chunked inclusive scan with carry, p_k = c_k / k, the maximum of p_k per highest recall
+// level reached (integer max on the bit pattern of a non-negative double: order-independent), then the 40-term sum.
+__global__ void __launch_bounds__(1024) k_ap_curve(const unsigned *sorted_tp, const long long *state, long long capacity, double *out_ap, long long *out_counts)
+{
+    __shared__ unsigned long long M[EV_LEVELS + 1];
+    __shared__ int wsum[16];
+    __shared__ long long carry_s;
+    const int t = blockIdx.x;
+    const int n = (int)max(0ll, min(state[0], capacity));
+    const long long n_gt = state[1];
+    if (threadIdx.x <= EV_LEVELS) M[threadIdx.x] = 0ull;
+    if (threadIdx.x == 0) carry_s = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int c0 = 0; c0 < n; c0 += 1024) {
+        const int k = c0 + threadIdx.x;
+        const bool bit = k < n && ((sorted_tp[k] >> t) & 1u);
+        const unsigned long long bal = __ballot(bit);
+        const int incl = __popcll(bal & ((2ull << lane) - 1));
+        if (lane == 0) wsum[wave] = __popcll(bal);
+        __syncthreads();
+        long long c = carry_s + incl;
+        for (int w = 0; w < wave; ++w) c += wsum[w];
+        if (k < n && n_gt > 0) {
+            const double p = (double)c / (double)(k + 1);
+            const long long j = min((long long)EV_LEVELS, 40 * c / n_gt);
+            atomicMax(&M[j], (unsigned long long)__double_as_longlong(p));
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) { int tot = 0; for (int w = 0; w < 16; ++w) tot += wsum[w]; carry_s += tot; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        double ap = __longlong_as_double(0x7ff8000000000000ll);
+        if (n_gt > 0) {
+            double sum = 0.0;
+            for (int j = 1; j <= EV_LEVELS; ++j) {
+                unsigned long long m = 0ull;
+                for (int q = j; q <= EV_LEVELS; ++q) m = max(m, M[q]);
+                sum += __longlong_as_double((long long)m);
+            }
+            ap = sum / 40.0;
+        }
+        out_ap[t] = ap;
+        out_counts[t] = carry_s;
+    }
+}
+
 }  // namespace
 
 extern "C" int dcf_eval_score_filter(const float *pred, int B, int h, int w, float thr, int cap, float *boxes, int32_t *count, dcf_stream_t stream)
@@ -282,7 +541,7 @@ extern "C" int dcf_eval_nms(const float *boxes, const int32_t *count_dev, int n_
                             void *ws, dcf_stream_t stream)
 {
     DCF_REQUIRE(boxes && keep && nkeep && ws && n_max >= 0 && n_max <= EV_CAP, "dcf_eval_nms: at most %d boxes per call (got %d)", EV_CAP, n_max);
-    DCF_REQUIRE(mode == 0 || mode == 1, "dcf_eval_nms: mode 0 = separating axes, 1 = 3-D IoU");
+    DCF_REQUIRE(mode == 0 || mode == 1 || mode == 2, "dcf_eval_nms: mode 0 = separating axes, 1 = 3-D IoU, 2 = bird's-eye IoU");
     hipStream_t s = S(stream);
     if (n_max == 0) { DCF_HIP(hipMemsetAsync(nkeep, 0, sizeof(int32_t), s)); return DCF_OK; }
     const int words = (n_max + 63) / 64;
@@ -302,5 +561,74 @@ extern "C" int dcf_eval_match(const float *pred_boxes, int npred, const float *r
     DCF_REQUIRE(pred_boxes, "dcf_eval_match: null predictions");
     hipStream_t s = S(stream);
     DCF_LAUNCH("eval_match", s, hipLaunchKernelGGL(k_eval_match, dim3(cdiv(npred, 256)), dim3(256), 0, s, pred_boxes, npred, ref_boxes, nref_rows, thresholds_dev, nthr, tp_counters));
+    return DCF_OK;
+}
+
+// ------------------------------------------------------------------ ranked evaluation: entries
+extern "C" size_t dcf_eval_rank_workspace_bytes(int B, int h, int w)
+{
+    return 8 * (size_t)B * 2 * (size_t)h * (size_t)w + 64;
+}
+
+extern "C" int dcf_eval_rank_filter(const float *pred, int B, int h, int w, float thr, int cap, float *boxes, float *scores, int32_t *count, int32_t *total,
+                                    void *ws, dcf_stream_t stream)
+{
+    DCF_REQUIRE(pred && boxes && scores && count && total && ws && B > 0 && B <= 65535 && h > 0 && w > 0 && cap > 0 && (int64_t)h * w <= (1 << 29),
+                "dcf_eval_rank_filter: bad arguments");
+    hipStream_t s = S(stream);
+    const int hw = h * w;
+    unsigned long long *keys = (unsigned long long *)ws;
+    DCF_LAUNCH_B("eval_rank_compact", (double)B * hw * 2 * 4.0, s, hipLaunchKernelGGL(k_rank_compact, dim3(B), dim3(1024), 0, s, pred, hw, thr, cap, keys, count, total));
+    DCF_LAUNCH("eval_rank_place", s, hipLaunchKernelGGL(k_rank_place, dim3(cdiv(2 * (int64_t)hw, 256), B), dim3(256), 0, s, pred, hw, cap, keys, total, boxes, scores));
+    return DCF_OK;
+}
+
+extern "C" size_t dcf_eval_match_ranked_workspace_bytes(int n_max, int R)
+{
+    return 8 * (size_t)(n_max > 0 ? n_max : 0) * (size_t)(R > 0 ? R : 0) + 64;
+}
+
+extern "C" int dcf_eval_match_ranked(const float *boxes, const int32_t *keep, const int32_t *count_dev, int n_max, const float *refs, int R,
+                                     const double *thresholds_dev, int nthr, uint32_t *tpmask, void *ws, dcf_stream_t stream)
+{
+    DCF_REQUIRE(boxes && keep && count_dev && thresholds_dev && tpmask && ws && n_max > 0 && n_max <= EV_CAP && R >= 0 && R <= 4096 && nthr >= 1 && nthr <= 16,
+                "dcf_eval_match_ranked: at most %d boxes, 4096 label rows and 16 thresholds per call (got %d, %d, %d)", EV_CAP, n_max, R, nthr);
+    DCF_REQUIRE(R == 0 || refs, "dcf_eval_match_ranked: null label rows");
+    hipStream_t s = S(stream);
+    double *iou = (double *)ws;
+    if (R > 0)
+        DCF_LAUNCH("eval_rank_iou", s, hipLaunchKernelGGL(k_rank_iou, dim3(cdiv((int64_t)n_max * R, 256)), dim3(256), 0, s, boxes, keep, count_dev, n_max, refs, R, iou));
+    DCF_LAUNCH("eval_rank_match", s, hipLaunchKernelGGL(k_rank_match, dim3(1), dim3(64 * nthr), 0, s, iou, keep, count_dev, n_max, R, thresholds_dev, nthr, tpmask));
+    return DCF_OK;
+}
+
+extern "C" int dcf_eval_accumulate(const float *scores, const uint32_t *tpmask, const int32_t *keep, const int32_t *count_dev, const int32_t *total_dev, int n_max,
+                                   const float *refs, int R, float *acc_scores, uint32_t *acc_tpmask, int64_t capacity, int64_t *state, dcf_stream_t stream)
+{
+    DCF_REQUIRE(scores && tpmask && keep && count_dev && total_dev && acc_scores && acc_tpmask && state && n_max > 0 && n_max <= EV_CAP && R >= 0 &&
+                capacity > 0 && capacity <= (1 << 30), "dcf_eval_accumulate: bad arguments");
+    DCF_REQUIRE(R == 0 || refs, "dcf_eval_accumulate: null label rows");
+    hipStream_t s = S(stream);
+    DCF_LAUNCH("eval_accumulate", s, hipLaunchKernelGGL(k_rank_accumulate, dim3(1), dim3(1024), 0, s, scores, tpmask, keep, count_dev, total_dev, n_max, refs, R,
+                                                        acc_scores, acc_tpmask, (long long)capacity, (long long *)state));
+    return DCF_OK;
+}
+
+extern "C" size_t dcf_eval_ap_workspace_bytes(int64_t capacity)
+{
+    return 4 * (size_t)(capacity > 0 ? capacity : 0) + 64;
+}
+
+extern "C" int dcf_eval_ap(const float *acc_scores, const uint32_t *acc_tpmask, const int64_t *state, int64_t capacity, int nthr, double *out_ap,
+                           int64_t *out_counts, void *ws, dcf_stream_t stream)
+{
+    DCF_REQUIRE(acc_scores && acc_tpmask && state && out_ap && out_counts && ws && capacity > 0 && capacity <= (1 << 30) && nthr >= 1 && nthr <= 32,
+                "dcf_eval_ap: bad arguments");
+    hipStream_t s = S(stream);
+    unsigned *sorted_tp = (unsigned *)ws;
+    DCF_LAUNCH("eval_ap_rank", s, hipLaunchKernelGGL(k_ap_rank, dim3(cdiv(capacity, 256)), dim3(256), 0, s, acc_scores, acc_tpmask, (const long long *)state,
+                                                     (long long)capacity, sorted_tp));
+    DCF_LAUNCH("eval_ap_curve", s, hipLaunchKernelGGL(k_ap_curve, dim3(nthr), dim3(1024), 0, s, sorted_tp, (const long long *)state, (long long)capacity, out_ap,
+                                                      (long long *)out_counts));
     return DCF_OK;
 }

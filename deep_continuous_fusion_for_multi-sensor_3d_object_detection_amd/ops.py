@@ -787,7 +787,8 @@ def eval_score_filter(pred, threshold, cap=EVAL_NMS_CAP):
 
 def eval_nms(boxes, mode, iou_threshold=0.01, count=None):
     """Greedy suppression in input order (test.py:110-175): boxes [n,7] fp32 on the device -> keep flags int32 [n].
-    mode "sat" | "iou"; count: optional int32 [1] device tensor with the number of valid rows."""
+    mode "sat" | "iou" | "bev" (bird's-eye IoU of the (x, y) rectangles, the ranked evaluation's: rows are then in rank order);
+    count: optional int32 [1] device tensor with the number of valid rows."""
     n = boxes.shape[0]
     if n > EVAL_NMS_CAP:
         raise H.DcfError("eval_nms: at most %d boxes per call (got %d)" % (EVAL_NMS_CAP, n))
@@ -795,7 +796,7 @@ def eval_nms(boxes, mode, iou_threshold=0.01, count=None):
     keep = torch.zeros((max(n, 1),), dtype=torch.int32, device=boxes.device)
     nkeep = torch.zeros((1,), dtype=torch.int32, device=boxes.device)
     ws = torch.empty((H.lib().dcf_eval_nms_workspace_bytes(max(n, 1)),), dtype=torch.uint8, device=boxes.device)
-    H.call("dcf_eval_nms", boxes, count, n, {"sat": 0, "iou": 1}[mode], float(iou_threshold), keep, nkeep, ws, H.stream_ptr())
+    H.call("dcf_eval_nms", boxes, count, n, {"sat": 0, "iou": 1, "bev": 2}[mode], float(iou_threshold), keep, nkeep, ws, H.stream_ptr())
     return keep[:n], nkeep
 
 
@@ -808,3 +809,57 @@ def eval_match(pred_boxes, ref_boxes, thresholds, tp):
     H.call("dcf_eval_match", _chk(pred_boxes.float().contiguous(), "pred_boxes"), n, _chk(ref_boxes.float().contiguous(), "ref_boxes"),
            ref_boxes.shape[0], thresholds, thresholds.shape[0], tp, H.stream_ptr())
     return tp
+
+
+# ------------------------------------------------------------------ ranked evaluation (eval_metric: ranked)
+def eval_rank_filter(pred, threshold, cap=EVAL_NMS_CAP):
+    """pred [B,32,h,w] fp32 -> (boxes [B,cap,7], scores [B,cap], count int32 [B], total int32 [B]): per sample the candidates with
+    score > threshold in rank order (score descending, ties to the lower candidate index); total = how many passed,
+    count = min(total, cap) -- exactly the cap highest-ranked are kept when total exceeds it."""
+    B, C, h, w = pred.shape
+    if C != 32 or pred.dtype != torch.float32:
+        raise H.DcfError("eval_rank_filter: pred must be the model output [B,32,h,w] fp32")
+    if not 0 < cap <= EVAL_NMS_CAP:
+        raise H.DcfError("eval_rank_filter: cap must be in 1..%d (got %d)" % (EVAL_NMS_CAP, cap))
+    pred = _chk(pred.contiguous(), "pred")
+    dev = pred.device
+    boxes = torch.zeros((B, cap, 7), dtype=torch.float32, device=dev)
+    scores = torch.zeros((B, cap), dtype=torch.float32, device=dev)
+    count = torch.zeros((B,), dtype=torch.int32, device=dev)
+    total = torch.zeros((B,), dtype=torch.int32, device=dev)
+    ws = torch.empty((H.lib().dcf_eval_rank_workspace_bytes(B, h, w),), dtype=torch.uint8, device=dev)
+    H.call("dcf_eval_rank_filter", pred, B, h, w, float(threshold), cap, boxes, scores, count, total, ws, H.stream_ptr())
+    return boxes, scores, count, total
+
+
+def eval_match_ranked(boxes, keep, count, ref_boxes, thresholds):
+    """One-to-one matching of the survivors (keep flags of eval_nms over boxes [n,7], count int32 [1] valid rows) against the
+    labelled rows of ref_boxes [R,9], per threshold of thresholds (fp64 device tensor, at most 16): tpmask int32 [n], bit t set
+    iff the survivor is a true positive at thresholds[t] (the bits of a uint32)."""
+    n, R = boxes.shape[0], ref_boxes.shape[0]
+    tpmask = torch.zeros((max(n, 1),), dtype=torch.int32, device=boxes.device)
+    if n == 0:
+        return tpmask[:0]
+    ws = torch.empty((H.lib().dcf_eval_match_ranked_workspace_bytes(n, R),), dtype=torch.uint8, device=boxes.device)
+    H.call("dcf_eval_match_ranked", _chk(boxes, "boxes"), _chk(keep, "keep"), count, n, _chk(ref_boxes, "ref_boxes") if R else None, R,
+           thresholds, thresholds.shape[0], tpmask, ws, H.stream_ptr())
+    return tpmask
+
+
+def eval_accumulate(scores, tpmask, keep, count, total, ref_boxes, acc_scores, acc_tpmask, state):
+    """Appends (score, tpmask) of one sample's survivors, in order, to acc_scores fp32 / acc_tpmask int32 [capacity] at the device
+    cursor state[0]; state int64 [4] = (cursor, labelled rows seen, samples with total > len(scores), unused).  The cursor counts
+    on past the capacity; nothing is written past it."""
+    n, R = scores.shape[0], ref_boxes.shape[0]
+    H.call("dcf_eval_accumulate", _chk(scores, "scores"), _chk(tpmask, "tpmask"), _chk(keep, "keep"), count, total, n,
+           _chk(ref_boxes, "ref_boxes") if R else None, R, acc_scores, acc_tpmask, acc_scores.shape[0], state, H.stream_ptr())
+
+
+def eval_ap(acc_scores, acc_tpmask, state, nthr):
+    """KITTI R40 average precision of the accumulated detections: (ap fp64 [nthr], tp int64 [nthr]) on the device."""
+    cap = acc_scores.shape[0]
+    ap = torch.zeros((nthr,), dtype=torch.float64, device=acc_scores.device)
+    tp = torch.zeros((nthr,), dtype=torch.int64, device=acc_scores.device)
+    ws = torch.empty((H.lib().dcf_eval_ap_workspace_bytes(cap),), dtype=torch.uint8, device=acc_scores.device)
+    H.call("dcf_eval_ap", _chk(acc_scores, "acc_scores"), _chk(acc_tpmask, "acc_tpmask"), _chk(state, "state"), cap, nthr, ap, tp, ws, H.stream_ptr())
+    return ap, tp

@@ -9,12 +9,17 @@ per-box TP history (test.py:204 appends the same dict object every time) -- pinn
 Boxes that live on the GPU take the HIP kernels of csrc/evalpost.hip (score filter + compaction, pairwise overlap
 matrix + one-wave greedy scan, bird's-eye-IoU matching); boxes handed over as host tensors take the numpy statement
 of the same definitions (evalgeom.py), which is also what the device kernels are checked against.
+
+RankedTest (`eval_metric: ranked`) is the evaluator the reference never built, next to the compat one:
+suppression in score order on the (x, y) bird's-eye IoU, one-to-one matching against the labels and KITTI R40 average precision,
+accumulated on the device and read once in summary().  evalrank.py is its host statement.
 """
 import numpy as np
 import torch
 import torch.nn as nn
 
 from . import evalgeom as EG
+from . import evalrank as ER
 from .loss import LossTotal
 
 
@@ -190,3 +195,145 @@ class Test(nn.Module):
         self.refined_bbox = self.NMS_SAT(boxes_nms)
         self.precision_recall_singleshot(self.refined_bbox, object_data.detach().float().cpu())
         return self.loss_value.item(), boxes
+
+
+class RankedTest(Test):
+    """`eval_metric: ranked`: candidates ranked by score, greedy suppression on the (x, y) bird's-eye IoU, one-to-one matching per
+    IoU threshold, KITTI R40 average precision (definitions: evalrank.py).  accumulate() enqueues one batch on the device without
+    waiting for it; summary() is the one synchronisation.  CPU tensors take the numpy statement."""
+
+    def _settings(self):
+        c = self.config
+        thr = c.get("eval_score_threshold")
+        return (float(c["score_threshold"] if thr is None else thr), float(c.get("eval_nms_iou", 0.1)),
+                int(c.get("eval_max_candidates", 4096)), int(c.get("eval_max_detections", 131072)))
+
+    def initialize_ap(self):
+        super(RankedTest, self).initialize_ap()
+        self._last = None
+        self._summary = None
+        acc = getattr(self, "_acc", None)
+        if acc is not None:                                     # allocated lazily by the first accumulate()
+            if acc["device"].type == "cuda":
+                acc["state"].zero_()
+            else:
+                acc["state"][:] = 0
+
+    def _accumulators(self, device):
+        cap = self._settings()[3]
+        acc = getattr(self, "_acc", None)
+        if acc is None or acc["device"] != device or acc["scores"].shape[0] != cap:
+            if device.type == "cuda":
+                acc = {"device": device, "scores": torch.zeros(cap, dtype=torch.float32, device=device),
+                       "tpmask": torch.zeros(cap, dtype=torch.int32, device=device), "state": torch.zeros(4, dtype=torch.int64, device=device),
+                       "thr": torch.tensor(self.IOU_threshold, dtype=torch.float64, device=device)}
+            else:
+                acc = {"device": device, "scores": np.zeros(cap, dtype=np.float32), "tpmask": np.zeros(cap, dtype=np.uint32),
+                       "state": np.zeros(4, dtype=np.int64)}
+            self._acc = acc
+        return acc
+
+    def accumulate(self, pred, object_data):
+        """One batch: rank filter, then per sample suppression, matching and the append to the accumulators.  pred [B,32,h,w] fp32
+        (the model output), object_data [B,R,9] label rows.  Nothing here waits for the device."""
+        thr, nms_iou, cap, _ = self._settings()
+        acc = self._accumulators(pred.device)
+        self._summary = None
+        if pred.is_cuda:
+            from . import ops
+            refs = object_data.to(device=pred.device, dtype=torch.float32).contiguous()
+            boxes, scores, count, total = ops.eval_rank_filter(pred.float(), thr, cap)
+            keeps = []
+            for b in range(pred.shape[0]):
+                keep, _ = ops.eval_nms(boxes[b], "bev", nms_iou, count=count[b:b + 1])
+                tpmask = ops.eval_match_ranked(boxes[b], keep, count[b:b + 1], refs[b], acc["thr"])
+                ops.eval_accumulate(scores[b], tpmask, keep, count[b:b + 1], total[b:b + 1], refs[b], acc["scores"], acc["tpmask"], acc["state"])
+                keeps.append(keep)
+            self._last = (boxes, scores, count, keeps)
+            return boxes, count
+        refs = object_data.detach().float().numpy()
+        boxes, scores, count, total = ER.rank_filter(pred.detach().float().numpy(), thr, cap)
+        keeps = []
+        st, capd = acc["state"], acc["scores"].shape[0]
+        for b in range(pred.shape[0]):
+            n = int(count[b])
+            keep = ER.nms(boxes[b, :n], nms_iou)
+            tpmask = ER.match(boxes[b, :n], keep, refs[b], self.IOU_threshold)
+            for i in np.nonzero(keep)[0]:
+                if st[0] < capd:
+                    acc["scores"][st[0]], acc["tpmask"][st[0]] = scores[b, i], tpmask[i]
+                st[0] += 1                                      # keeps counting past the capacity: summary() raises
+            st[1] += int((refs[b][:, 8] == 1).sum())
+            st[2] += int(total[b] > cap)
+            keeps.append(keep)
+        self._last = (boxes, scores, count, keeps)
+        return boxes, count
+
+    def summary(self):
+        """The one synchronisation: average precision per IoU threshold (KITTI R40), their mean, and the totals."""
+        if self._summary is not None:
+            return self._summary
+        acc = getattr(self, "_acc", None)
+        thr = self.IOU_threshold
+        if acc is None:
+            out = ER.summarize(np.zeros(0, np.float32), np.zeros(0, np.uint32), 0, thr)
+        elif acc["device"].type == "cuda":
+            from . import ops
+            ap, tp = ops.eval_ap(acc["scores"], acc["tpmask"], acc["state"], len(thr))
+            state = acc["state"].cpu().tolist()
+            self._check_capacity(state[0], acc["scores"].shape[0])
+            out = ER.assemble(ap.cpu().numpy(), tp.cpu().numpy(), state[0], state[1], thr, state[2])
+        else:
+            state = acc["state"].tolist()
+            self._check_capacity(state[0], acc["scores"].shape[0])
+            out = ER.summarize(acc["scores"][:state[0]], acc["tpmask"][:state[0]], state[1], thr, state[2])
+        self.num_P, self.num_T = out["num_P"], out["num_T"]
+        self.num_TP_set = dict(out["tp"])
+        self._summary = out
+        return out
+
+    @staticmethod
+    def _check_capacity(cursor, capacity):
+        if cursor > capacity:
+            raise RuntimeError("RankedTest: %d detections accumulated, eval_max_detections holds %d: raise it (nothing is dropped silently)"
+                               % (cursor, capacity))
+
+    def get_num_TP_set(self):
+        self.summary()
+        return self.num_TP_set
+
+    def get_num_T(self):
+        self.summary()
+        return self.num_T
+
+    def get_num_P(self):
+        self.summary()
+        return self.num_P
+
+    def detections(self):
+        """Per sample (boxes [k,7], scores [k]) of the last batch's survivors, in rank order.  Synchronises: for inspection."""
+        if self._last is None:
+            return []
+        boxes, scores, count, keeps = self._last
+        out = []
+        for b in range(len(keeps)):
+            if isinstance(boxes, torch.Tensor):
+                sel = keeps[b].bool()
+                sel[int(count[b]):] = False
+                out.append((boxes[b][sel], scores[b][sel]))
+            else:
+                sel = np.zeros(boxes.shape[1], dtype=bool)
+                sel[:len(keeps[b])] = keeps[b] != 0
+                out.append((torch.from_numpy(boxes[b][sel]), torch.from_numpy(scores[b][sel])))
+        return out
+
+    def get_eval_value_onestep(self, lidar_voxel, camera_image, object_data, num_ref_box, **extra):
+        with torch.no_grad():
+            pred = self.net(lidar_voxel, camera_image, **extra)
+            pred_cls, pred_reg, pred_bbox = torch.split(pred, [4, 14, 14], dim=1)
+            self.loss_value = self.loss_total(object_data.to(pred.device), num_ref_box, pred_cls, pred_reg)
+            boxes, count = self.accumulate(pred, object_data)
+        value = self.loss_value.item()                          # the caller's loss value: the step's one wait, after everything is enqueued
+        n = count.cpu().tolist() if isinstance(count, torch.Tensor) else count.tolist()
+        cand = [boxes[b, :n[b]] if isinstance(boxes, torch.Tensor) else torch.from_numpy(boxes[b, :n[b]]) for b in range(pred.shape[0])]
+        return value, cand

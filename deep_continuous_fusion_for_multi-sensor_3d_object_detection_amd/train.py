@@ -529,14 +529,31 @@ def evaluate(training, tester, dataset, loader, max_batches=None):
         cum += value
         if max_batches is not None and n >= max_batches:
             break
-    tester.display_average_precision()
+    if hasattr(tester, "summary"):                                         # eval_metric: ranked (test.RankedTest): the one synchronisation
+        tester.summary()
+    else:
+        tester.display_average_precision()
     return cum / max(n, 1), cum, tester.get_num_P(), tester.get_num_T(), tester.get_num_TP_set()
+
+
+def make_tester(model, config):
+    """test.Test (`eval_metric` absent or compat: the reference's post-processing) or test.RankedTest (`eval_metric: ranked`)."""
+    from .test import RankedTest, Test
+    metric = config.get("eval_metric") or "compat"
+    if metric not in ("compat", "ranked"):
+        raise ValueError("eval_metric must be compat or ranked (got %r)" % (metric,))
+    return (RankedTest if metric == "ranked" else Test)(model, config)
+
+
+def _print_ranked(tester):
+    if hasattr(tester, "summary"):
+        s = tester.summary()
+        print("    AP (R40) %s, mAP %.4f" % ({t: round(v, 4) for t, v in s["ap"].items()}, s["map"]))
 
 
 def main():
     import yaml
     from .frame_loader import FrameLoader
-    from .test import Test
     here = os.path.dirname(os.path.abspath(__file__))
     with open(os.path.join(here, "config", "config_carla.yaml")) as f:
         config = yaml.safe_load(f)
@@ -549,7 +566,7 @@ def main():
     training = Train(config)
     # the reference builds Test(training.model) before the loop (train.py:76), which is what puts the trained module in eval
     # mode: bn_mode "eval" is the default here, and with bn_mode "module" this constructor has the same effect
-    tester = Test(training.model, config)
+    tester = make_tester(training.model, config)
     test_dataset = make_dataset(config, "test") if rank0 else None
     test_loader = FrameLoader(test_dataset, config["batch_size"], shuffle=False, num_workers=int(config.get("num_workers", 4)),
                               drop_last=True) if rank0 else None
@@ -571,11 +588,13 @@ def main():
                 if rank0:
                     mean, cum, npos, nt, tp = evaluate(training, tester, test_dataset, test_loader, max_batches=int(config.get("eval_batches", 7)))           # `batch_ndx_ > 5`
                     print("batch %d: validation loss %.4f, positives %d, labelled %d, TP@0.5 %d" % (batch_ndx, mean, npos, nt, tp[0.5]))
+                    _print_ranked(tester)
                 _eval_barrier()
         _eval_barrier()
         if rank0:                                                          # train.py:105-122
             mean, cum, npos, nt, tp = evaluate(training, tester, test_dataset, test_loader, max_batches=int(config.get("eval_batches_epoch", 12)))   # `batch_ndx > 10`
             print("epoch %d: validation loss %.4f (cumulative %.2f), positives %d, labelled %d, TP %s" % (epoch, mean, cum, npos, nt, dict(tp)))
+            _print_ranked(tester)
         _eval_barrier()
 
 

@@ -572,7 +572,7 @@ int dcf_loss_hard_fwd_bwd_det(const float *cls, int64_t cls_bstride, const float
  *   order, then anchor 1's; count_out[b] = how many passed (may exceed cap: rows past cap are dropped).
  * dcf_eval_nms: test.py:110-175.  Greedy suppression in INPUT order: keep[i] = 1 iff box i overlaps no earlier kept box.
  *   mode 0 = separating-axis test of the bird's-eye rectangles (NMS_SAT; touching counts), mode 1 = 3-D IoU > iou_threshold with the
- *   kept box's centre nudged by 1e-4 (NMS_IOU).  boxes [n_max][7] fp32 (x, y, z, l, w, h, yaw); count_dev (may be NULL) = number of
+ *   kept box's centre nudged by 1e-4 (NMS_IOU), mode 2 = see the ranked evaluation below.  boxes [n_max][7] fp32 (x, y, z, l, w, h, yaw); count_dev (may be NULL) = number of
  *   valid rows on the device; n_max <= 4096.  ws: dcf_eval_nms_workspace_bytes(n_max).
  * dcf_eval_match: test.py:177-206.  tp_counters[t] += number of predictions whose bird's-eye IoU with any labelled box
  *   (ref row [9], last column == 1) exceeds thresholds_dev[t] (fp64, on the device). */
@@ -583,6 +583,37 @@ int dcf_eval_nms(const float *boxes, const int32_t *count_dev, int n_max, int mo
                  void *ws, dcf_stream_t stream);
 int dcf_eval_match(const float *pred_boxes, int npred, const float *ref_boxes, int nref_rows, const double *thresholds_dev, int nthr,
                    int32_t *tp_counters, dcf_stream_t stream);
+
+/* (version 202 still: added without a new minor) Ranked evaluation (`eval_metric: ranked`): score-ordered
+ * suppression, one-to-one matching and KITTI R40 average precision, decided on integer keys and fp64 geometry; evalrank.py is the
+ * host statement.  A candidate is (anchor a, pixel px) of a sample, index a*h*w + px; its key is
+ * (orderable_u32(score) << 32) | (0xFFFFFFFF - index), larger first (score descending, ties to the lower index).
+ * dcf_eval_rank_filter: the candidates with score > threshold in rank order: boxes_out [B][cap][7], scores_out [B][cap];
+ *   total_out[b] = how many passed, count_out[b] = min(total, cap); with total > cap exactly the cap highest-ranked are written.  Rows
+ *   >= count are left untouched.  ws: dcf_eval_rank_workspace_bytes(B, h, w).
+ * dcf_eval_nms mode 2: bird's-eye IoU of the (x, y) rectangles > iou_threshold (no nudge; a zero-area box gives NaN = no overlap).
+ * dcf_eval_match_ranked: per threshold t (bit t of tpmask[i], at most 16), the survivors (keep[i] != 0, i < *count_dev) in row order
+ *   each take the labelled row (ref row [9], last column == 1) of highest bird's-eye IoU among the rows not yet taken at t (ties: the
+ *   lower row); the pair counts iff that IoU > thresholds_dev[t], and only then is the row taken.  tpmask [n_max] receives rows
+ *   < *count_dev.  n_max <= 4096, R <= 4096.  ws: dcf_eval_match_ranked_workspace_bytes(n_max, R).
+ * dcf_eval_accumulate: appends (score, tpmask) of one sample's survivors, in order, at state[0] of acc_scores / acc_tpmask
+ *   [capacity]; state (int64 [4], on the device) = {cursor, labelled rows seen, samples with total > n_max, unused}.  The cursor keeps
+ *   counting past capacity; nothing is written past it.
+ * dcf_eval_ap: the min(cursor, capacity) detections ordered by (score descending, accumulation index ascending); per threshold t
+ *   out_counts[t] = c_N and out_ap[t] = (P_1 + ... + P_40) / 40 with P_j = max{ c_k / k : 40 c_k >= j n_gt } (0 for the empty set;
+ *   NaN when n_gt == 0).  ws: dcf_eval_ap_workspace_bytes(capacity). */
+size_t dcf_eval_rank_workspace_bytes(int B, int h, int w);
+int dcf_eval_rank_filter(const float *pred, int B, int h, int w, float threshold, int cap, float *boxes_out, float *scores_out,
+                         int32_t *count_out, int32_t *total_out, void *ws, dcf_stream_t stream);
+size_t dcf_eval_match_ranked_workspace_bytes(int n_max, int R);
+int dcf_eval_match_ranked(const float *boxes, const int32_t *keep, const int32_t *count_dev, int n_max, const float *ref_boxes, int R,
+                          const double *thresholds_dev, int nthr, uint32_t *tpmask, void *ws, dcf_stream_t stream);
+int dcf_eval_accumulate(const float *scores, const uint32_t *tpmask, const int32_t *keep, const int32_t *count_dev, const int32_t *total_dev,
+                        int n_max, const float *ref_boxes, int R, float *acc_scores, uint32_t *acc_tpmask, int64_t capacity, int64_t *state,
+                        dcf_stream_t stream);
+size_t dcf_eval_ap_workspace_bytes(int64_t capacity);
+int dcf_eval_ap(const float *acc_scores, const uint32_t *acc_tpmask, const int64_t *state, int64_t capacity, int nthr, double *out_ap,
+                int64_t *out_counts, void *ws, dcf_stream_t stream);
 
 #ifdef __cplusplus
 }
