@@ -97,6 +97,15 @@ static inline hipStream_t S(dcf_stream_t s) { return (hipStream_t)s; }
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 static inline double esize_of(int dtype) { return dtype == DCF_F32 ? 4.0 : 2.0; }
 
+// the 64-bit finaliser of every stateless hash of the library (loss sampling: csrc/loss.hip; point drop: csrc/geometry.hip)
+__host__ __device__ inline uint64_t dcf_mix64(uint64_t z)
+{
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
 // ---------------------------------------------------------------- dtype helpers
 typedef unsigned short bf16_t;  // raw bits
 

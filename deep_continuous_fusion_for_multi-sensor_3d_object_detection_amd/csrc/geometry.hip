@@ -257,6 +257,68 @@ __global__ void __launch_bounds__(CP_THREADS) k_proj_scatter_b(ProjBatch pb, Lim
 }
 
 // ------------------------------------------------------------------------------
+// Train-time BEV augmentation (host statement: augment.py).  p' = A p with A = s R(theta) F given as the
+// five fp32 numbers a00 a01 a10 a11 a22, every product and sum rounded where augment.transform_points rounds it.  A point whose
+// drop hash falls under the frame's threshold is written as (+inf, +inf, +inf): in_range() compares strictly, so the voxeliser,
+// the projection and the range filter reject it as they are, nothing is compacted and the point counts stay host-known.
+// One launch for the frames of a batch (blockIdx.y = frame, per-frame values by value, static selection as in proj_pred_of);
+// a thread loads its AUG_ITEMS points, then stores them: it reads and writes its own points only, so out == pts is allowed.
+// Dword accesses: a frame starts at any point offset of a larger buffer, i.e. nothing beyond 4-byte alignment is known.
+// ------------------------------------------------------------------------------
+constexpr int AUG_THREADS = 256;
+constexpr int AUG_ITEMS = 4;
+constexpr int AUG_TILE = AUG_THREADS * AUG_ITEMS;
+struct AugBatch {
+    const float *pts[DCF_PROJ_BATCH_MAX];
+    float *out[DCF_PROJ_BATCH_MAX];
+    unsigned long long key[DCF_PROJ_BATCH_MAX];
+    int n[DCF_PROJ_BATCH_MAX];
+    unsigned thr[DCF_PROJ_BATCH_MAX];
+    float m[DCF_PROJ_BATCH_MAX][5];
+};
+
+__global__ void __launch_bounds__(AUG_THREADS) k_augment_points_b(AugBatch ab)
+{
+    const int b = blockIdx.y;
+    const float *pts = nullptr;
+    float *out = nullptr;
+    unsigned long long key = 0;
+    int n = 0;
+    unsigned thr = 0;
+    float a00 = 0.f, a01 = 0.f, a10 = 0.f, a11 = 0.f, a22 = 0.f;
+#pragma unroll
+    for (int f = 0; f < DCF_PROJ_BATCH_MAX; ++f)
+        if (f == b) {
+            pts = ab.pts[f]; out = ab.out[f]; key = ab.key[f]; n = ab.n[f]; thr = ab.thr[f];
+            a00 = ab.m[f][0]; a01 = ab.m[f][1]; a10 = ab.m[f][2]; a11 = ab.m[f][3]; a22 = ab.m[f][4];
+        }
+    const long long base = (long long)blockIdx.x * AUG_TILE + threadIdx.x;
+    if (base >= n) return;
+    float x[AUG_ITEMS], y[AUG_ITEMS], z[AUG_ITEMS];
+#pragma unroll
+    for (int k = 0; k < AUG_ITEMS; ++k) {
+        const long long i = base + k * AUG_THREADS;
+        if (i < n) {
+            const float *q = pts + 3 * (size_t)i;
+            x[k] = q[0]; y[k] = q[1]; z[k] = q[2];
+        }
+    }
+    const float inf = __int_as_float(0x7f800000);
+#pragma unroll
+    for (int k = 0; k < AUG_ITEMS; ++k) {
+        const long long i = base + k * AUG_THREADS;
+        if (i < n) {
+            const bool drop = (unsigned)(dcf_mix64(key ^ dcf_mix64((unsigned long long)i)) >> 32) < thr;
+            const float xo = __fadd_rn(__fmul_rn(a00, x[k]), __fmul_rn(a01, y[k]));
+            const float yo = __fadd_rn(__fmul_rn(a10, x[k]), __fmul_rn(a11, y[k]));
+            const float zo = __fmul_rn(a22, z[k]);
+            float *q = out + 3 * (size_t)i;
+            q[0] = drop ? inf : xo; q[1] = drop ? inf : yo; q[2] = drop ? inf : zo;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------
 // Voxeliser.  data_import_carla.py:236-258.
 // ------------------------------------------------------------------------------
 struct Corner8 {
@@ -1483,6 +1545,48 @@ extern "C" int dcf_project_filter_batch(const float *const *pts, const int *n, i
     DCF_LAUNCH("compact_scan", s, hipLaunchKernelGGL(k_proj_scan_b, dim3(1, B), dim3(CP_THREADS), 0, s, bs, nb, bstride, count_dev));
     DCF_LAUNCH_B("project_scatter", (double)nmax * B * (12.0 + 20.0), s, hipLaunchKernelGGL(k_proj_scatter_b, dim3(nb, B), dim3(CP_THREADS), 0, s, pb, l, ulim, vlim, mode, bs, bstride,
                                                                                     uv_out, xyz_out, rows));
+    return DCF_OK;
+}
+
+// Train-time augmentation of the B frames of a batch in one launch.  pts / n / mat / drop_key / drop_thresh: HOST arrays (B device
+// pointers, B counts, B x {a00 a01 a10 a11 a22}, B hash keys, B thresholds = floor(p * 2^32) capped at 2^32 - 1); out: B device
+// pointers, out[b] == pts[b] (in place) or a range that overlaps no frame's input or output.  Bit for bit augment.transform_points
+// with the rows outside augment.keep_mask set to +inf.
+extern "C" int dcf_augment_points_batch(const float *const *pts, const int *n, int B, const float *mat, const uint64_t *drop_key,
+                                        const uint32_t *drop_thresh, float *const *out, dcf_stream_t stream)
+{
+    const char *who = "dcf_augment_points_batch";
+    DCF_REQUIRE(pts && n && mat && drop_key && drop_thresh && out, "%s: bad arguments", who);
+    DCF_REQUIRE(B >= 1 && B <= DCF_PROJ_BATCH_MAX, "%s: 1..%d frames per call", who, DCF_PROJ_BATCH_MAX);
+    AugBatch ab;
+    int nmax = 0;
+    double total = 0.0;
+    for (int b = 0; b < DCF_PROJ_BATCH_MAX; ++b) {
+        const bool live = b < B;
+        DCF_REQUIRE(!live || (n[b] >= 0 && (n[b] == 0 || (pts[b] && out[b]))), "%s: frame %d: bad point count / null points", who, b);
+        DCF_REQUIRE(!live || ((((uintptr_t)pts[b]) | ((uintptr_t)out[b])) & 3) == 0, "%s: frame %d: pointers must be 4-byte aligned", who, b);
+        ab.pts[b] = live ? pts[b] : nullptr;
+        ab.out[b] = live ? out[b] : nullptr;
+        ab.key[b] = live ? drop_key[b] : 0;
+        ab.n[b] = live ? n[b] : 0;
+        ab.thr[b] = live ? drop_thresh[b] : 0;
+        for (int k = 0; k < 5; ++k) ab.m[b][k] = live ? mat[5 * b + k] : 0.f;
+        if (live && n[b] > nmax) nmax = n[b];
+        if (live) total += n[b];
+    }
+    // an output may alias its own frame's input exactly; every other overlap of an output with an input or another output is a race
+    for (int b = 0; b < B; ++b)
+        for (int c = 0; c < B; ++c) {
+            if (!n[b] || !n[c]) continue;
+            const uintptr_t o0 = (uintptr_t)out[b], o1 = o0 + 12 * (uintptr_t)n[b];
+            const uintptr_t p0 = (uintptr_t)pts[c], p1 = p0 + 12 * (uintptr_t)n[c];
+            const uintptr_t q0 = (uintptr_t)out[c], q1 = q0 + 12 * (uintptr_t)n[c];
+            DCF_REQUIRE((b == c && o0 == p0) || o1 <= p0 || p1 <= o0, "%s: output of frame %d overlaps the input of frame %d", who, b, c);
+            DCF_REQUIRE(b == c || o1 <= q0 || q1 <= o0, "%s: outputs of frames %d and %d overlap", who, b, c);
+        }
+    if (nmax == 0) return DCF_OK;
+    hipStream_t s = S(stream);
+    DCF_LAUNCH_B("augment_points", total * 24.0, s, hipLaunchKernelGGL(k_augment_points_b, dim3(cdiv(nmax, AUG_TILE), B), dim3(AUG_THREADS), 0, s, ab));
     return DCF_OK;
 }
 

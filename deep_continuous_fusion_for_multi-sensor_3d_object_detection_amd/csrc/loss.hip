@@ -231,13 +231,7 @@ __global__ void k_loss_rows_fold(const float *rows, int n, float *loss)
 // bit.  Semantics kept from the reference: the positive list has one entry per (box, window cell) (overlapping windows give a
 // cell twice), the subset is uniform without replacement over ENTRIES (loss.py:107-110: shuffle, truncate), negatives are
 // drawn with replacement and rejected only against the selected positives (loss.py:117-126).
-__host__ __device__ inline uint64_t dcf_mix64(uint64_t z)
-{
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
+// (dcf_mix64: dcf_common.h -- the point-drop hash of csrc/geometry.hip is the same function)
 __host__ __device__ inline uint32_t dcf_loss_rand(uint64_t seed, int sample, int stream, int index, int attempt)
 {
     const uint64_t ctr = ((uint64_t)(uint32_t)sample << 44) | ((uint64_t)(uint32_t)stream << 40) | ((uint64_t)(uint32_t)attempt << 20) | (uint64_t)(uint32_t)index;

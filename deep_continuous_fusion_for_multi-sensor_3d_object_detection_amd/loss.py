@@ -79,7 +79,7 @@ def pack_lists(samples):
 
 
 def _mix64(z):
-    """dcf_mix64 of csrc/loss.hip on uint64 arrays (numpy wraps modulo 2^64)."""
+    """dcf_mix64 of csrc/dcf_common.h on uint64 arrays (numpy wraps modulo 2^64)."""
     z = z + np.uint64(0x9E3779B97F4A7C15)
     z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
     z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)

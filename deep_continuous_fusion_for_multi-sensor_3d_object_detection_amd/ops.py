@@ -437,6 +437,36 @@ def project_filter_batch(pts_list, lim, crts, ulim, vlim, mode, uv_all, xyz_all,
     return ws
 
 
+def augment_points_batch(pts_list, params, out_list=None):
+    """Train-time BEV augmentation (augment.py) of the frames of a batch: pts_list = B device tensors [n_b,3]
+    fp32 (views at any point offset of a larger buffer included), params = B augment.draw results; out_list: B tensors to write
+    into (None = in place).  Bit for bit augment.transform_points, dropped points (augment.keep_mask) as +inf rows.  One launch
+    per 8 frames.  Returns out_list."""
+    from . import augment
+    B = len(pts_list)
+    if len(params) != B or (out_list is not None and len(out_list) != B):
+        raise H.DcfError("augment_points_batch: %d frames, %d parameter sets" % (B, len(params)))
+    out_list = pts_list if out_list is None else out_list
+    for p, o in zip(pts_list, out_list):
+        for t in (p, o):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
+                raise H.DcfError("augment_points_batch: frames must be contiguous fp32 CUDA tensors")
+        if o.numel() < p.numel():
+            raise H.DcfError("augment_points_batch: output smaller than its frame")
+    for b0 in range(0, B, 8):
+        sl = slice(b0, min(b0 + 8, B))
+        k = sl.stop - sl.start
+        ptrs = (ctypes.c_void_p * k)(*[p.data_ptr() if p.shape[0] else None for p in pts_list[sl]])
+        outs = (ctypes.c_void_p * k)(*[o.data_ptr() if p.shape[0] else None for p, o in zip(pts_list[sl], out_list[sl])])
+        ns = (ctypes.c_int * k)(*[int(p.shape[0]) for p in pts_list[sl]])
+        mat = np.ascontiguousarray(np.stack([augment.matrix5(q) for q in params[sl]], 0), dtype=np.float32)
+        keys = (ctypes.c_uint64 * k)(*[int(q["drop_key"]) for q in params[sl]])
+        thr = (ctypes.c_uint32 * k)(*[augment.drop_threshold(q) for q in params[sl]])
+        H.call("dcf_augment_points_batch", ctypes.addressof(ptrs), ctypes.addressof(ns), k, mat, ctypes.addressof(keys), ctypes.addressof(thr),
+               ctypes.addressof(outs), H.stream_ptr())
+    return out_list
+
+
 def knn_bev(xyz, cnt, K, h, w, stride, aff, rmax=None, ws=None, out=None):
     """out: optional int32 [K,h,w] tensor to write into (e.g. a frame's slice of a batch tensor)."""
     n_max = xyz.shape[0]

@@ -6,6 +6,7 @@ the reference's single-process DDP wrapper (train.py:24, which current torch rej
 """
 import os
 
+import numpy as np
 import torch
 import torch.distributed as dist
 import torch.nn as nn
@@ -67,6 +68,65 @@ def parse_guard_config(cfg):
         return None
     return {"mode": mode, "scale": scale, "growth_factor": growth, "backoff_factor": backoff, "growth_interval": gi,
             "max_norm": clip}
+
+
+AUGMENT_KEYS = ("enabled", "seed", "rotation_deg", "scale", "flip_prob", "point_drop")
+
+
+def parse_augment_config(config):
+    """The `augment` block (config_carla.yaml; augment.py), validated: None = off (no block, or enabled:
+    false), else {"seed", "rotation_deg", "scale": (lo, hi), "flip_prob", "point_drop": (lo, hi)}.  Bad values raise ValueError
+    whether the block is enabled or not -- augmentation is never switched off quietly."""
+    import math
+    blk = config.get("augment", None)
+    if blk is None:
+        return None
+    if not isinstance(blk, dict):
+        raise ValueError("augment must be a mapping (got %r)" % (blk,))
+    unknown = sorted(set(blk) - set(AUGMENT_KEYS))
+    if unknown:
+        raise ValueError("augment: unknown keys %s (known: %s)" % (unknown, list(AUGMENT_KEYS)))
+
+    def number(key, v):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError("augment.%s must be a number (got %r)" % (key, v))
+        if not math.isfinite(float(v)):
+            raise ValueError("augment.%s must be finite (got %r)" % (key, v))
+        return float(v)
+
+    def interval(key, default):
+        v = blk.get(key, default)
+        if not isinstance(v, (list, tuple)) or len(v) != 2:
+            raise ValueError("augment.%s must be [lo, hi] (got %r)" % (key, v))
+        lo, hi = number(key, v[0]), number(key, v[1])
+        if lo > hi:
+            raise ValueError("augment.%s: lo > hi (got %r)" % (key, v))
+        return lo, hi
+
+    def probability(key, v):
+        if not 0.0 <= v <= 1.0:
+            raise ValueError("augment.%s must be a probability in [0, 1] (got %r)" % (key, v))
+        return v
+
+    enabled = blk.get("enabled", False)
+    if not isinstance(enabled, bool):
+        raise ValueError("augment.enabled must be true or false (got %r)" % (enabled,))
+    seed = blk.get("seed", 0)
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise ValueError("augment.seed must be an integer (got %r)" % (seed,))
+    rot = number("rotation_deg", blk.get("rotation_deg", 0.0))
+    if rot < 0.0:
+        raise ValueError("augment.rotation_deg: theta ~ U(-r, +r) needs r >= 0 (got %r)" % (rot,))
+    scale = interval("scale", (1.0, 1.0))
+    if scale[0] <= 0.0:
+        raise ValueError("augment.scale must be positive (got %r)" % (blk.get("scale"),))
+    flip = probability("flip_prob", number("flip_prob", blk.get("flip_prob", 0.0)))
+    drop = interval("point_drop", (0.0, 0.0))
+    probability("point_drop", drop[0])
+    probability("point_drop", drop[1])
+    if not enabled:
+        return None
+    return {"seed": int(seed), "rotation_deg": rot, "scale": scale, "flip_prob": flip, "point_drop": drop}
 
 
 class FlatAdam(object):
@@ -185,6 +245,10 @@ class Train(nn.Module):
             raise ValueError("grad_bucket_dtype must be f32 or bf16 (got %r)" % (self.grad_bucket_dtype,))
         self._g16 = None
         self._pending, self._reduced, self._widen = [], 0, []
+        # train-time BEV augmentation (augment.py; None = off, the default): one_step_raw draws the frames' parameters from
+        # (seed, rank, aug_calls, frame) -- no generator state, the count is all a checkpoint has to carry
+        self.augment = parse_augment_config(config)
+        self.aug_calls = 0
 
     def sync_replicas(self):
         """Identical replicas: rank 0's parameters, buffers, optimiser moments and step count win (called at construction;
@@ -227,12 +291,15 @@ class Train(nn.Module):
             self._geo_sets[key] = st
         return st
 
-    def geometry_async(self, frame_geometry, points_list, crts=None, wait_event=None):
+    def geometry_async(self, frame_geometry, points_list, crts=None, wait_event=None, augment=None):
         """Per-frame geometry (voxelise, project, KNN of the fusion sites) on a side HIP stream, so that these
         small latency-bound kernels overlap the camera stream's convolutions on the compute stream.
         Returns (x_lidar [B,Cz,L,W], geom) where geom carries the events the engine waits on.
         crts: optional per-frame [4,3] projection matrices (KITTI calibrates every frame).
         wait_event: event the side stream has to wait for before it reads the points (FrameLoader's H2D copies).
+        augment: optional per-frame parameters (augment.draw): the side stream first writes the augmented points (dropped ones
+        as +inf rows, which every range test rejects) into a persistent buffer of the geometry set, and everything below runs
+        on those, with projection matrices that keep every point on the pixel of its original (augment.compose_crt).
         The returned tensors live in one of two persistent buffer sets (config static_geometry, default on): they stay
         valid until the second-next call."""
         main = torch.cuda.current_stream()
@@ -261,6 +328,19 @@ class Train(nn.Module):
             st["used"] = True
         with torch.cuda.stream(self._side):
             pcs, uvs, cnts = [], [], []
+            if augment is not None:
+                from . import augment as AUG
+                if len(augment) != Bn:
+                    raise ValueError("augment: %d parameter sets for %d frames" % (len(augment), Bn))
+                src = [frame_geometry._pts(p) for p in points_list]
+                if st is not None:                      # fixed addresses; a frame over max_num_pc takes the allocating path
+                    if "aug" not in st:
+                        st["aug"] = torch.empty((Bn, mp, 3), dtype=torch.float32, device=src[0].device)
+                    dst = [st["aug"][b, :p.shape[0]] for b, p in enumerate(src)]
+                else:
+                    dst = [torch.empty_like(p) for p in src]
+                points_list = ops.augment_points_batch(src, list(augment), dst)
+                crts = [AUG.compose_crt(frame_geometry.crt if (crts is None or crts[b] is None) else crts[b], augment[b]) for b in range(Bn)]
             if st is not None:
                 x_lidar = st["x_lidar"]
                 st["proj"].zero_()
@@ -407,8 +487,25 @@ class Train(nn.Module):
     def one_step_raw(self, frame_geometry, batch):
         """One train step from a FrameLoader batch (raw points + image in HBM): geometry on the side stream, then one_step."""
         batch.wait()
-        x_lidar, geom = self.geometry_async(frame_geometry, batch["points"], crts=batch.get("crt"), wait_event=batch.event)
-        self.one_step(x_lidar, batch["image"], batch["bboxes"], batch["num_bboxes"], geom=geom)
+        boxes, nums, params = batch["bboxes"], batch["num_bboxes"], None
+        if self.augment is not None:
+            params, boxes, nums = self._draw_augment(frame_geometry, boxes, nums)
+        x_lidar, geom = self.geometry_async(frame_geometry, batch["points"], crts=batch.get("crt"), wait_event=batch.event, augment=params)
+        self.one_step(x_lidar, batch["image"], boxes, nums, geom=geom)
+
+    def _draw_augment(self, frame_geometry, boxes, nums):
+        """This step's per-frame augmentation parameters and the labels under them (host tensors of max_num_bbox rows: no device
+        read, no synchronisation); counts the call."""
+        from . import augment as AUG
+        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        Bn = int(boxes.shape[0])
+        params = [AUG.draw(self.augment, self.augment["seed"], rank, self.aug_calls, b) for b in range(Bn)]
+        self.aug_calls += 1
+        src, cnt = boxes.detach().cpu().numpy(), [int(v) for v in torch.as_tensor(nums).reshape(-1)]
+        moved = [AUG.transform_boxes(src[b], cnt[b], params[b], frame_geometry.config) for b in range(Bn)]
+        new_boxes = torch.from_numpy(np.stack([m[0] for m in moved], 0)).to(boxes.dtype)
+        new_nums = torch.tensor([m[1] for m in moved], dtype=torch.as_tensor(nums).dtype)
+        return params, new_boxes, new_nums
 
     # ------------------------------------------------------------------ guarded step: device-side read-outs (no synchronisation)
     def loss_scale(self):
@@ -431,7 +528,8 @@ class Train(nn.Module):
         opt = {"step": self.optimizer.step_count, "m": self.optimizer.m.cpu(), "v": self.optimizer.v.cpu()}
         if self.optimizer.amp is not None:         # the guard state (scale, growth tracker, counters), without the partials workspace
             opt["amp"] = self.optimizer.amp.header.cpu()
-        torch.save({"model": sd, "optimizer": opt, "epoch": int(epoch), "loss_calls": int(getattr(self.loss_total, "calls", 0))}, path)
+        torch.save({"model": sd, "optimizer": opt, "epoch": int(epoch), "loss_calls": int(getattr(self.loss_total, "calls", 0)),
+                    "aug_calls": int(self.aug_calls)}, path)
 
     def load_checkpoint(self, path):
         ck = torch.load(path, map_location="cpu")
@@ -446,6 +544,7 @@ class Train(nn.Module):
             self.optimizer.amp.header.copy_(amp)    # a checkpoint without it keeps the configured initial scale
         if hasattr(self.loss_total, "calls"):       # device sampling: a resumed run continues the draw sequence instead of replaying it
             self.loss_total.calls = int(ck.get("loss_calls", self.optimizer.step_count))
+        self.aug_calls = int(ck.get("aug_calls", self.optimizer.step_count))    # augmentation: the draw sequence continues likewise
         return int(ck.get("epoch", 0))
 
     def get_loss_value(self, lidar_voxel, camera_image, object_data, num_ref_box, **extra):

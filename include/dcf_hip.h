@@ -99,6 +99,17 @@ int dcf_project_filter(const float *pts, int n, const float *lim, const float *c
 int dcf_project_filter_batch(const float *const *pts, const int *n, int B, const float *lim, const float *crt, float ulim, float vlim,
                              int mode, float *uv_out, float *xyz_out, int rows, int32_t *count_dev, void *ws, dcf_stream_t stream);
 
+/* Train-time BEV augmentation of the B (<= 8) frames of a batch in one launch (host statement: augment.py).
+ * pts / out: HOST arrays of B device pointers to [n[b]][3] points (4-byte alignment is all that is assumed; out[b] == pts[b] is
+ * allowed, any other overlap is refused); n HOST int[B] (0 is legal); mat HOST float[B][5] = {a00, a01, a10, a11, a22} of
+ * A = s R(theta) diag(1, f, 1) rounded once to fp32; drop_key HOST uint64[B], drop_thresh HOST uint32[B].
+ *   x' = fl(fl(a00 x) + fl(a01 y))   y' = fl(fl(a10 x) + fl(a11 y))   z' = fl(a22 z)          (no contraction)
+ * Point i of frame b is dropped iff (mix64(drop_key[b] ^ mix64(i)) >> 32) < drop_thresh[b] (mix64: the finaliser of the loss
+ * sampler's hash) and is then written as (+inf, +inf, +inf), which every range test of this library rejects: nothing is
+ * compacted, the point counts do not change. */
+int dcf_augment_points_batch(const float *const *pts, const int *n, int B, const float *mat, const uint64_t *drop_key,
+                             const uint32_t *drop_thresh, float *const *out, dcf_stream_t stream);
+
 /* BEV K-nearest-neighbour (reference: model.py:199-203 TODO; spec SURVEY.md App. D).
  * xyz [n_max][3], first *count_dev rows valid.  idx_out int32 [K][h][w], -1 padding.
  * rmax2 < 0 = unbounded.  K <= 8.  ws: dcf_knn_workspace_bytes(n_max,h,w). */

@@ -1,0 +1,116 @@
+#!/usr/bin/env python3
+"""Cost of the train-time BEV augmentation (csrc/geometry.hip k_augment_points_b) at cfg2.
+
+  python tools/augment_bench.py [--iters 300] [--steps 40] [--warmup 10] [--rounds 3] [--out FILE]
+
+1. The launch alone: dcf_augment_points_batch on cfg2's 100 000 points x batch 2 (rotation + scale + flip + point drop, out of place
+   into fixed buffers, as Train.geometry_async issues it), HIP events around every launch after a warm-up, the median.
+2. The whole cfg2 train step (bench.py's frames resident in HBM, batch 2, bf16) through Train.one_step_raw with `augment` off, on
+   with ranges that draw the identity (same frames, same downstream work: the feature's own cost) and on with real ranges (rotated
+   frames lose points to the range and image tests, so the step has less to do): three trainers in one process on one GPU,
+   alternating, --rounds rounds of --steps steps each, a host clock around steps that end in a device synchronise.
+Prints one JSON line (and writes it to --out)."""
+import argparse
+import importlib
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = "deep_continuous_fusion_for_multi-sensor_3d_object_detection_amd"
+AUGMENT = dict(enabled=True, seed=1, rotation_deg=45.0, scale=[0.95, 1.05], flip_prob=0.5, point_drop=[0.0, 0.1])
+# the block switched on with ranges that draw the identity: the pass, the per-frame matrices and the label work are all there, the
+# frames and so everything downstream are the un-augmented step's -- the cost of the feature apart from what it does to the workload
+NEUTRAL = dict(enabled=True, seed=1, rotation_deg=0.0, scale=[1.0, 1.0], flip_prob=0.0, point_drop=[0.0, 0.0])
+SIDES = (("off", None), ("neutral", NEUTRAL), ("on", AUGMENT))
+
+
+def launch_alone(pool, iters, warmup=50):
+    import torch
+    A, ops = importlib.import_module(PKG + ".augment"), importlib.import_module(PKG + ".ops")
+    frames = [pool.pts[0], pool.pts[1]]
+    outs = [torch.empty_like(f) for f in frames]
+    params = [A.draw(AUGMENT, 1, 0, 0, b) for b in range(2)]
+    for _ in range(warmup):
+        ops.augment_points_batch(frames, params, outs)
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+    for a, b in ev:
+        a.record()
+        ops.augment_points_batch(frames, params, outs)
+        b.record()
+    torch.cuda.synchronize()
+    us = sorted(a.elapsed_time(b) * 1e3 for a, b in ev)
+    nbytes = sum(f.numel() for f in frames) * 4 * 2
+    med = statistics.median(us)
+    return {"points": [int(f.shape[0]) for f in frames], "iters": iters, "median_us": med, "p10_us": us[len(us) // 10], "p90_us": us[len(us) * 9 // 10],
+            "bytes": nbytes, "gbytes_per_s_at_median": nbytes / med / 1e3}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=300)
+    ap.add_argument("--steps", type=int, default=40)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("augment_bench.py measures on the GPU; none is visible")
+    bench = importlib.import_module("bench")
+    T, FL, det = (importlib.import_module(PKG + "." + m) for m in ("train", "frame_loader", "detfill"))
+    B = 2
+    cfg = bench.kitti_config(B)
+    pool = bench.FramePool(cfg, 4, 100000, 1234)
+    out = {"launch": launch_alone(pool, args.iters)}
+
+    trainers = {}
+    for side, block in SIDES:
+        c = dict(cfg)
+        if block is not None:
+            c["augment"] = dict(block)
+        trainers[side] = T.Train(c)
+        det.fill_state_dict(trainers[side].model)
+
+    def batch(step):
+        ids = pool.batch(step, B)
+        b = FL.Batch(bboxes=torch.stack([pool.boxes[i] for i in ids], 0), num_bboxes=torch.tensor([pool.nb[i] for i in ids]), crt=None)
+        b["points"], b["image"] = [pool.pts[i] for i in ids], pool.image_batch(ids)
+        return b
+
+    def run(side, steps):
+        tr = trainers[side]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for s in range(steps):
+            tr.one_step_raw(pool.geometry, batch(s))
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) * 1e3 / steps
+        tr._last_cnt = next(st for st in tr._geo_sets.values() if st["slot"] == tr._geo_slot)["cnt_host"].clone()   # points that reached the fusion sites
+        return dt
+
+    np.random.seed(0)
+    for side, _ in SIDES:
+        run(side, args.warmup)
+    series = {side: [] for side, _ in SIDES}
+    for _ in range(args.rounds):
+        for side, _ in SIDES:
+            series[side].append(run(side, args.steps))
+    out["step"] = {"batch": B, "dtype": cfg["dtype"], "steps_per_round": args.steps, "augment": AUGMENT, "ms_per_step": series,
+                   "median_ms": {side: statistics.median(v) for side, v in series.items()},
+                   "valid_points_last_step": {side: [int(v) for v in tr._last_cnt.tolist()] for side, tr in trainers.items()},
+                   "loss": {side: float(tr.loss_value.item()) for side, tr in trainers.items()}}
+    line = json.dumps(out)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
