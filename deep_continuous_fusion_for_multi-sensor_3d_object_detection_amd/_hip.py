@@ -141,6 +141,8 @@ SIGNATURES = {
     "dcf_grad_stats": (c_int, [P, c_i64, P, P]),
     "dcf_amp_update": (c_int, [P, c_float, c_int, ctypes.c_double, ctypes.c_double, c_int, c_float, c_float, c_float, c_float, P]),
     "dcf_adam_step_guarded": (c_int, [P, P, P, P, c_i64, c_float, c_float, c_float, P, P]),
+    # training recipe: AdamW decay + weight EMA in the Adam pass (csrc/optim.hip)
+    "dcf_adamw_ema_step": (c_int, [P, P, P, P, P, P, c_i64, c_float, c_float, c_float, c_float, c_int, c_float, c_float, c_float, P, P]),
 }
 
 

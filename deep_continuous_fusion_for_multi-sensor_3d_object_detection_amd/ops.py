@@ -325,6 +325,15 @@ def adam_step_guarded(params, grads, m, v, beta1, beta2, eps, state):
     H.call("dcf_adam_step_guarded", params, grads, m, v, params.numel(), beta1, beta2, eps, state.raw, H.stream_ptr())
 
 
+def adamw_ema_step(params, grads, m, v, lr, beta1, beta2, eps, step, gscale=1.0, decay_mul=1.0, decay_bits=None, ema=None, ema_omd=0.0,
+                   state=None):
+    """dcf_adamw_ema_step (csrc/optim.hip): the Adam step with decoupled weight decay (decay_mul = 1 - lr * weight_decay on the
+    float4 groups whose bit is set in the uint64 device tensor decay_bits; None = all) and the weight average ema += ema_omd *
+    (p' - ema) in the same pass.  state (AmpState): the guarded step -- lr, step and gscale then come from the device."""
+    H.call("dcf_adamw_ema_step", params, grads, m, v, ema, decay_bits, params.numel(), lr, beta1, beta2, eps, step, gscale, decay_mul,
+           ema_omd, None if state is None else state.raw, H.stream_ptr())
+
+
 # ------------------------------------------------------------------ geometry
 class GridSpec(object):
     """Grid constants of CarlaDataset.__init__ (data_import_carla.py:35-43) and the filter

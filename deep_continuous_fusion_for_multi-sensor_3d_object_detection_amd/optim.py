@@ -1,0 +1,158 @@
+"""Host statements of the training recipe: learning-rate schedule, decoupled weight decay, weight EMA.
+
+Plain Python / numpy, no device: the trainer (train.FlatAdam) evaluates them per optimiser call and hands the results to the
+optimiser kernels by value (csrc/optim.hip, dcf_adamw_ema_step).  The clock of all three is the HOST's count of optimiser
+calls k = 0, 1, 2, ... -- a step the device-side guard skips still advances it, as a torch scheduler stepped beside GradScaler
+does -- so nothing here ever reads the device.
+"""
+import math
+
+import numpy as np
+
+SCHEDULE_KEYS = ("kind", "warmup_steps", "warmup_start_factor", "milestones", "gamma", "total_steps", "min_lr")
+SCHEDULE_KINDS = ("constant", "step", "cosine")
+
+
+def _number(name, v):
+    if isinstance(v, bool) or not isinstance(v, (int, float)):
+        raise ValueError("%s must be a number (got %r)" % (name, v))
+    if not math.isfinite(float(v)):
+        raise ValueError("%s must be finite (got %r)" % (name, v))
+    if v < 0:
+        raise ValueError("%s must not be negative (got %r)" % (name, v))
+    return float(v)
+
+
+def _count(name, v):
+    if isinstance(v, bool) or not isinstance(v, int):
+        raise ValueError("%s must be an integer (got %r)" % (name, v))
+    if v < 0:
+        raise ValueError("%s must not be negative (got %r)" % (name, v))
+    return int(v)
+
+
+def _flag(name, v):
+    if not isinstance(v, bool):
+        raise ValueError("%s must be true or false (got %r)" % (name, v))
+    return v
+
+
+def parse_schedule(blk):
+    """The `lr_schedule` block, validated: None (absent) or {"kind", "warmup_steps", "warmup_start_factor", "milestones", "gamma",
+    "total_steps", "min_lr"}."""
+    if blk is None:
+        return None
+    if not isinstance(blk, dict):
+        raise ValueError("lr_schedule must be a mapping (got %r)" % (blk,))
+    unknown = sorted(set(blk) - set(SCHEDULE_KEYS))
+    if unknown:
+        raise ValueError("lr_schedule: unknown keys %s (known: %s)" % (unknown, list(SCHEDULE_KEYS)))
+    kind = blk.get("kind", "constant")
+    if kind not in SCHEDULE_KINDS:
+        raise ValueError("lr_schedule.kind must be one of %s (got %r)" % (list(SCHEDULE_KINDS), kind))
+    warm = _count("lr_schedule.warmup_steps", blk.get("warmup_steps", 0))
+    f0 = _number("lr_schedule.warmup_start_factor", blk.get("warmup_start_factor", 0.0))
+    if f0 > 1.0:
+        raise ValueError("lr_schedule.warmup_start_factor must be in [0, 1] (got %r)" % (f0,))
+    ms = blk.get("milestones", [])
+    if not isinstance(ms, (list, tuple)):
+        raise ValueError("lr_schedule.milestones must be a list (got %r)" % (ms,))
+    ms = [_count("lr_schedule.milestones", m) for m in ms]
+    if any(b < a for a, b in zip(ms, ms[1:])):
+        raise ValueError("lr_schedule.milestones must be sorted (got %r)" % (ms,))
+    gamma = _number("lr_schedule.gamma", blk.get("gamma", 0.1))
+    min_lr = _number("lr_schedule.min_lr", blk.get("min_lr", 0.0))
+    total = blk.get("total_steps", None)
+    if total is not None:
+        total = _count("lr_schedule.total_steps", total)
+    if kind == "cosine":
+        if total is None:
+            raise ValueError("lr_schedule: kind cosine needs total_steps")
+        if total <= warm:
+            raise ValueError("lr_schedule: total_steps (%d) must exceed warmup_steps (%d)" % (total, warm))
+    return {"kind": kind, "warmup_steps": warm, "warmup_start_factor": f0, "milestones": tuple(ms), "gamma": gamma,
+            "total_steps": total, "min_lr": min_lr}
+
+
+def parse_optim_config(config):
+    """The recipe's keys (config_carla.yaml), validated when the trainer is built.  None = none of them configured (the optimiser
+    then makes exactly the launches it made before the recipe existed); else
+      {"schedule": parse_schedule's block or None, "weight_decay", "weight_decay_exclude": tuple of substrings,
+       "ema_decay": None or d in [0, 1), "ema_warmup", "ema_eval"}.
+    Bad values raise ValueError whether or not the feature they belong to is enabled."""
+    sched = parse_schedule(config.get("lr_schedule", None))
+    wd = config.get("weight_decay", 0.0)
+    wd = 0.0 if wd is None else _number("weight_decay", wd)
+    ex = config.get("weight_decay_exclude", None)
+    if ex is None:
+        ex = []
+    if not isinstance(ex, (list, tuple)) or any(not isinstance(s, str) or not s for s in ex):
+        raise ValueError("weight_decay_exclude must be a list of non-empty strings (got %r)" % (ex,))
+    d = config.get("ema_decay", None)
+    if d is not None:
+        d = _number("ema_decay", d)
+        if d >= 1.0:
+            raise ValueError("ema_decay must be in [0, 1) (got %r)" % (d,))
+    warm = _flag("ema_warmup", config.get("ema_warmup", False))
+    ev = _flag("ema_eval", config.get("ema_eval", True))
+    if sched is None and wd == 0.0 and d is None:
+        return None
+    return {"schedule": sched, "weight_decay": wd, "weight_decay_exclude": tuple(ex), "ema_decay": d, "ema_warmup": warm,
+            "ema_eval": ev}
+
+
+def lr_at(sched, base_lr, k):
+    """Learning rate of optimiser call k (0-based), float64, a pure function of k.  sched None = the base rate."""
+    base = float(base_lr)
+    if sched is None:
+        return base
+    k = int(k)
+    warm = sched["warmup_steps"]
+    if k < warm:
+        f0 = sched["warmup_start_factor"]
+        return base * (f0 + (1.0 - f0) * k / warm)
+    j = k - warm
+    kind = sched["kind"]
+    if kind == "step":
+        return base * sched["gamma"] ** sum(1 for m in sched["milestones"] if m <= j)
+    if kind == "cosine":
+        T = sched["total_steps"] - warm
+        lo = sched["min_lr"]
+        return lo + (base - lo) * (1.0 + math.cos(math.pi * min(j, T) / T)) / 2.0
+    return base
+
+
+def ema_decay_at(cfg, k):
+    """Decay d_k of the weight average at optimiser call k: e' = d_k * e + (1 - d_k) * p'.  ema_warmup: min(d, (1 + k) / (10 + k)),
+    so that the first calls do not average in the initial weights with the full horizon."""
+    d = float(cfg["ema_decay"])
+    if cfg.get("ema_warmup", False):
+        d = min(d, (1.0 + k) / (10.0 + k))
+    return d
+
+
+def decays(key, shape, exclude=()):
+    """Decoupled weight decay applies to convolution and linear weights: tensors of two or more logical dimensions whose key
+    holds none of the `weight_decay_exclude` substrings.  Biases and BatchNorm affine parameters (1-D) never decay."""
+    return len(shape) >= 2 and not any(s in key for s in exclude)
+
+
+def decay_bits(table_entries, n_params, exclude=()):
+    """The decay mask of dcf_adamw_ema_step from engine.ParamTable.entries [(key, logical shape, offset, physical numel, layout)]:
+    uint64 words, one bit per float4 group (group j = arena elements 4j .. 4j+3 = bit j % 64 of word j / 64).  A decaying tensor
+    sets the bits of its whole PHYSICAL extent (`ohwi` and `stem` layouts included: the stem's zero padding stays zero under a
+    multiply, and so do the up to three padding elements behind a tensor).  ParamTable keeps every tensor 16-byte aligned, so no
+    group holds elements of two tensors."""
+    groups = (int(n_params) + 3) // 4
+    bits = np.zeros(groups, dtype=bool)
+    for key, shape, off, n, layout in table_entries:
+        if off % 4:
+            raise ValueError("parameter %s starts at element %d: not 16-byte aligned" % (key, off))
+        if off + n > n_params:
+            raise ValueError("parameter %s ends behind the arena (%d + %d > %d)" % (key, off, n, n_params))
+        if decays(key, shape, exclude):
+            bits[off // 4:(off + n + 3) // 4] = True
+    padded = np.zeros((groups + 63) // 64 * 64, dtype=np.uint8)
+    padded[:groups] = bits
+    by = np.packbits(padded.reshape(-1, 64), axis=1, bitorder="little")        # byte b of a word = its bits 8b .. 8b+7
+    return np.ascontiguousarray(by).view("<u8").astype(np.uint64).reshape(-1)

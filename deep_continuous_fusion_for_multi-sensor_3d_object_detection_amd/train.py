@@ -4,6 +4,7 @@ One process per GPU (torchrun); gradients live in the model's flat arena, so dat
 is ONE RCCL all-reduce of that arena per step followed by ONE fused Adam launch -- instead of
 the reference's single-process DDP wrapper (train.py:24, which current torch rejects).
 """
+import contextlib
 import os
 
 import numpy as np
@@ -12,6 +13,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from . import ops
+from . import optim as OPT
 from .loss import LossTotal
 from ._hip import torch_dtype as H_torch_dtype
 from .model import ObjectDetection_DCF, parse_deterministic_config
@@ -132,15 +134,40 @@ def parse_augment_config(config):
 class FlatAdam(object):
     """Adam(lr, betas=(beta1, 0.999), eps=1e-8) of train.py:28 on the flat parameter arena.
     guard (parse_guard_config): the guarded step of csrc/amp.hip -- loss scale, non-finite skip and clipping decided on the
-    device; the bias-correction count is then the device's applied-step count (step_count reads it: a synchronisation)."""
+    device; the bias-correction count is then the device's applied-step count (step_count reads it: a synchronisation).
+    recipe (optim.parse_optim_config): `lr` is then the BASE rate and call k runs at optim.lr_at(schedule, lr,
+    k), k = opt_calls, the host's count of step() calls (a step the guard skips on the device still counts; the bias correction
+    keeps the applied count).  With weight_decay > 0 or ema_decay set the step is dcf_adamw_ema_step (csrc/optim.hip) instead of
+    dcf_adam_step / dcf_adam_step_guarded: decoupled decay on the tensors of optim.decay_bits, and `ema`, a second arena that
+    follows the parameters, both in the Adam pass.  None: the launches, arguments and allocations of the plain optimiser."""
 
-    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, guard=None):
+    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, guard=None, recipe=None):
         self.model, self.lr, self.betas, self.eps = model, lr, betas, eps
         self._step_count = 0
         self.m = torch.zeros_like(model.flat_params)
         self.v = torch.zeros_like(model.flat_params)
         self.guard = guard
         self.amp = ops.AmpState(model.flat_params.device, guard["scale"]) if guard is not None else None
+        self.recipe = recipe
+        self.opt_calls = 0
+        self.ema = self.decay_bits = None
+        self._ema_fresh = False
+        if recipe is not None and recipe["weight_decay"] > 0.0:
+            words = OPT.decay_bits(model._table.entries, model.flat_params.numel(), recipe["weight_decay_exclude"])
+            self.decay_bits = torch.from_numpy(words.view(np.int64)).to(model.flat_params.device)
+        if recipe is not None and recipe["ema_decay"] is not None:
+            # until the first step() the average IS the parameters: weights loaded after construction are what it starts from
+            self.ema = model.flat_params.detach().clone()
+            self._ema_fresh = True
+        self.fused = self.decay_bits is not None or self.ema is not None
+
+    def seed_ema(self):
+        """Before the first optimiser call (or a checkpoint) the average follows the parameters; no-op afterwards."""
+        if self._ema_fresh:
+            self.ema.copy_(self.model.flat_params.detach())
+
+    def lr_at(self, k):
+        return OPT.lr_at(self.recipe["schedule"], self.lr, k) if self.recipe is not None else self.lr
 
     @property
     def step_count(self):
@@ -159,25 +186,53 @@ class FlatAdam(object):
         pass  # the backward pass overwrites the gradient arena
 
     def step(self, gscale=1.0):
+        k = self.opt_calls
+        self.opt_calls = k + 1
+        lr = self.lr_at(k)                      # by value into the launches below: the step runs outside the captured graphs
+        decay_mul, omd = 1.0, 0.0
+        if self.fused:
+            decay_mul = 1.0 - float(lr) * self.recipe["weight_decay"]         # AdamW's param.mul_(1 - lr * wd); rounded to fp32 at the call
+            if self.ema is not None:
+                self.seed_ema()
+                self._ema_fresh = False
+                omd = 1.0 - OPT.ema_decay_at(self.recipe, k)
         if self.amp is not None:
             g = self.guard
             ops.grad_stats(self.model.flat_grads, self.amp)
             ops.amp_update(self.amp, gscale, g["mode"] == "dynamic", g["growth_factor"], g["backoff_factor"], g["growth_interval"],
-                           g["max_norm"], self.lr, self.betas[0], self.betas[1])
-            ops.adam_step_guarded(self.model.flat_params, self.model.flat_grads, self.m, self.v, self.betas[0], self.betas[1],
-                                  self.eps, self.amp)
+                           g["max_norm"], lr, self.betas[0], self.betas[1])
+            if self.fused:
+                ops.adamw_ema_step(self.model.flat_params, self.model.flat_grads, self.m, self.v, lr, self.betas[0], self.betas[1],
+                                   self.eps, 0, gscale, decay_mul, self.decay_bits, self.ema, omd, self.amp)
+            else:
+                ops.adam_step_guarded(self.model.flat_params, self.model.flat_grads, self.m, self.v, self.betas[0], self.betas[1],
+                                      self.eps, self.amp)
             return
         self._step_count += 1
-        ops.adam_step(self.model.flat_params, self.model.flat_grads, self.m, self.v, self.lr, self.betas[0], self.betas[1],
-                      self.eps, self._step_count, gscale)
+        if self.fused:
+            ops.adamw_ema_step(self.model.flat_params, self.model.flat_grads, self.m, self.v, lr, self.betas[0], self.betas[1],
+                               self.eps, self._step_count, gscale, decay_mul, self.decay_bits, self.ema, omd)
+        else:
+            ops.adam_step(self.model.flat_params, self.model.flat_grads, self.m, self.v, lr, self.betas[0], self.betas[1],
+                          self.eps, self._step_count, gscale)
 
     def state_dict(self):
-        return {"step": self.step_count, "m": self.m, "v": self.v}
+        sd = {"step": self.step_count, "m": self.m, "v": self.v, "opt_calls": self.opt_calls}
+        if self.ema is not None:
+            self.seed_ema()
+            sd["ema"] = self.ema
+        return sd
 
     def load_state_dict(self, sd):
+        """A state written before the recipe existed has neither `opt_calls` nor `ema`: the clock then continues at the step
+        count and the average starts from the parameters as they are now (load the model first)."""
         self.step_count = int(sd["step"])
         self.m.copy_(sd["m"])
         self.v.copy_(sd["v"])
+        self.opt_calls = int(sd.get("opt_calls", sd["step"]))
+        if self.ema is not None:
+            self.ema.copy_(sd["ema"] if sd.get("ema") is not None else self.model.flat_params.detach())
+            self._ema_fresh = False
 
 
 def world():
@@ -223,7 +278,10 @@ class Train(nn.Module):
         self.loss_value = None
         # guarded optimiser step (loss_scale / grad_clip_norm; None = the plain Adam step, the default)
         self.guard = parse_guard_config(config)
-        self.optimizer = FlatAdam(self.model, config["learning_rate"], (config["beta1"], 0.999), guard=self.guard)
+        # training recipe (lr_schedule / weight_decay / ema_decay; None = the constant-rate Adam step, the default)
+        self.recipe = OPT.parse_optim_config(config)
+        self.optimizer = FlatAdam(self.model, config["learning_rate"], (config["beta1"], 0.999), guard=self.guard, recipe=self.recipe)
+        self._ema_swapped = False
         self.sync_replicas()
         self._side = None
         self.static_geometry = bool(config.get("static_geometry", True))
@@ -255,6 +313,15 @@ class Train(nn.Module):
         call it again after loading weights or a checkpoint on rank 0 only)."""
         for t in (self.model.flat_params, self.model._bufflat, self.optimizer.m, self.optimizer.v):
             broadcast_from_rank0(t)
+        if self.optimizer.ema is not None:       # the weight average, and below the clock of the schedule and of the average
+            self.optimizer.seed_ema()
+            broadcast_from_rank0(self.optimizer.ema)
+        if world() > 1:
+            oc = torch.tensor([self.optimizer.opt_calls], dtype=torch.int64)
+            if dist.get_backend() != "gloo":
+                oc = oc.to(self.model.flat_params.device)
+            dist.broadcast(oc, 0)
+            self.optimizer.opt_calls = int(oc.item())
         if self.optimizer.amp is not None:       # loss scale, growth tracker and step counters (the applied count included)
             broadcast_from_rank0(self.optimizer.amp.raw)
         elif world() > 1:                        # Adam's bias correction depends on it
@@ -442,6 +509,8 @@ class Train(nn.Module):
             self._reduced += b - a
 
     def one_step(self, lidar_voxel, camera_image, object_data, num_ref_box, **extra):
+        if self._ema_swapped:
+            raise RuntimeError("one_step inside ema_weights(): the parameter arena holds the averaged weights")
         pred_cls, pred_reg, _ = self._predict(lidar_voxel, camera_image, extra)
         self.loss_value = self.loss_total(object_data, num_ref_box, pred_cls, pred_reg)
         self.optimizer.zero_grad()
@@ -520,12 +589,69 @@ class Train(nn.Module):
         """Steps skipped for a non-finite gradient so far (device int64 tensor, a copy)."""
         return None if self.optimizer.amp is None else self.optimizer.amp.skipped_steps.clone()
 
+    # ------------------------------------------------------------------ training recipe: read-outs (no synchronisation)
+    def learning_rate(self):
+        """The rate the NEXT optimiser call runs at (host float: the schedule is a function of the host's call count)."""
+        return float(self.optimizer.lr_at(self.optimizer.opt_calls))
+
+    def ema_params(self):
+        """The averaged weights: a device arena laid out like model.flat_params (the tensor itself); None without ema_decay."""
+        if self.optimizer.ema is None:
+            return None
+        if self._ema_swapped:
+            raise RuntimeError("ema_params() inside ema_weights(): the arenas are exchanged")
+        self.optimizer.seed_ema()
+        return self.optimizer.ema
+
+    def ema_state_dict(self):
+        """The model's state_dict (the reference's key names) with the averaged weights for the parameters; buffers (BatchNorm
+        statistics) are the model's own.  None without ema_decay."""
+        ema = self.ema_params()
+        if ema is None:
+            return None
+        from .engine import ParamTable
+        sd = {k: v.detach() for k, v in self.model.state_dict().items()}
+        for key, shape, off, n, layout in self.model._table.entries:
+            sd[key] = ParamTable.view(ema, shape, off, n, layout)
+        return sd
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Run the body on the averaged weights: the CONTENTS of the parameter arena and of the EMA arena are exchanged in place and
+        exchanged back on exit (also on an exception).  No address changes, so captured graphs and the backend's tables stay valid;
+        the backend re-folds the weight images on the next forward by itself.  Does not nest; one_step inside raises."""
+        if self.optimizer.ema is None:
+            raise RuntimeError("ema_weights(): ema_decay is not configured")
+        if self._ema_swapped:
+            raise RuntimeError("ema_weights() does not nest")
+        self.optimizer.seed_ema()
+        p, e = self.model.flat_params.detach(), self.optimizer.ema
+
+        def exchange():
+            tmp = p.clone()
+            p.copy_(e)
+            e.copy_(tmp)
+
+        exchange()
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            exchange()
+            self._ema_swapped = False
+
     # ------------------------------------------------------------------ checkpoint / resume (SURVEY.md 8(f) N4)
     def save_checkpoint(self, path, epoch=0):
         """Model state_dict (the reference's key names, train.py:79) plus what the reference never saved:
         optimiser moments / step count and the epoch, so that training can really resume."""
         sd = {k: v.detach().clone().contiguous().cpu() for k, v in self.model.state_dict().items()}
-        opt = {"step": self.optimizer.step_count, "m": self.optimizer.m.cpu(), "v": self.optimizer.v.cpu()}
+        if self._ema_swapped:
+            raise RuntimeError("save_checkpoint inside ema_weights(): the arenas are exchanged")
+        opt = {"step": self.optimizer.step_count, "m": self.optimizer.m.cpu(), "v": self.optimizer.v.cpu(),
+               "opt_calls": int(self.optimizer.opt_calls)}
+        if self.optimizer.ema is not None:         # the weight average (the schedule's clock is opt_calls above)
+            self.optimizer.seed_ema()
+            opt["ema"] = self.optimizer.ema.cpu()
         if self.optimizer.amp is not None:         # the guard state (scale, growth tracker, counters), without the partials workspace
             opt["amp"] = self.optimizer.amp.header.cpu()
         torch.save({"model": sd, "optimizer": opt, "epoch": int(epoch), "loss_calls": int(getattr(self.loss_total, "calls", 0)),
@@ -621,13 +747,16 @@ def evaluate(training, tester, dataset, loader, max_batches=None):
     tester.initialize_ap()
     cum = 0.0
     n = 0
-    for n, batch in enumerate(loader, 1):
-        batch.wait()
-        x_lidar, geom = training.geometry_async(dataset.geometry, batch["points"], crts=batch.get("crt"), wait_event=batch.event)
-        value, _ = tester.get_eval_value_onestep(x_lidar, batch["image"], batch["bboxes"], batch["num_bboxes"], geom=geom)
-        cum += value
-        if max_batches is not None and n >= max_batches:
-            break
+    # ema_decay with ema_eval (default true): the pass runs on the averaged weights
+    averaged = getattr(training, "recipe", None) is not None and training.recipe["ema_decay"] is not None and training.recipe["ema_eval"]
+    with (training.ema_weights() if averaged else contextlib.nullcontext()):
+        for n, batch in enumerate(loader, 1):
+            batch.wait()
+            x_lidar, geom = training.geometry_async(dataset.geometry, batch["points"], crts=batch.get("crt"), wait_event=batch.event)
+            value, _ = tester.get_eval_value_onestep(x_lidar, batch["image"], batch["bboxes"], batch["num_bboxes"], geom=geom)
+            cum += value
+            if max_batches is not None and n >= max_batches:
+                break
     if hasattr(tester, "summary"):                                         # eval_metric: ranked (test.RankedTest): the one synchronisation
         tester.summary()
     else:
@@ -675,6 +804,9 @@ def main():
             sampler.set_epoch(epoch)
         if rank0:
             torch.save(training.model.state_dict(), "./saved_model/" + config["saved_model_name"])
+            if training.ema_params() is not None:                          # the averaged weights beside the model, same key names
+                torch.save(training.ema_state_dict(), "./saved_model/" + config["saved_model_name"] + "_ema")
+            print("epoch %d: learning rate %.6g" % (epoch, training.learning_rate()))
         for batch_ndx, batch in enumerate(loader):
             training.one_step_raw(dataset.geometry, batch)
             if batch_ndx % 100 == 0:

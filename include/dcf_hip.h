@@ -436,6 +436,24 @@ int dcf_amp_update(dcf_amp_state *state, float gscale_host, int dynamic, double 
 int dcf_adam_step_guarded(float *params, const float *grads, float *m, float *v, int64_t n, float beta1, float beta2, float eps,
                           const dcf_amp_state *state, dcf_stream_t stream);
 
+/* (version 202 still: added without a new minor) The training recipe's optimiser step (`lr_schedule` / `weight_decay` / `ema_decay`,
+ * DESIGN.md section 15; csrc/optim.hip): dcf_adam_step / dcf_adam_step_guarded with torch.optim.AdamW's decoupled weight decay and
+ * an exponential moving average of the parameters in the same pass.  Per element, fp32, nothing contracted, in this order:
+ *     gk = g * gscale ;  m' = b1*m + (1-b1)*gk ;  v' = b2*v + (1-b2)*gk*gk                    (dcf_adam_step's expressions)
+ *     q  = decays(i) ? p * decay_mul : p ;  p' = q - lr_over_bc1 * m' / (sqrtf(v') * inv_sqrt_bc2 + eps)
+ *     e' = e + ema_omd * (p' - e)                                                              (ema != NULL only)
+ * decay_mul = (float)(1 - lr * weight_decay) and ema_omd = (float)(1 - decay) come from the host.  state == NULL: lr_over_bc1 and
+ * inv_sqrt_bc2 are dcf_adam_step's host expressions for `step`.  state != NULL: those two and gscale are read from the state (lr,
+ * step and gscale are ignored), and with found_inf set NOTHING is stored -- not p, m, v and not ema.
+ * decay_bits: one bit per float4 group -- group j is elements 4j .. 4j+3, its bit is bit j % 64 of word j / 64 (ceil(ceil(n/4)/64)
+ * words; a tail group of fewer than four elements uses its bit like any other); NULL = every element decays.
+ * With decay_mul == 1, ema == NULL the stores are bit for bit dcf_adam_step's (state == NULL) / dcf_adam_step_guarded's.
+ * params, grads, m, v, ema 16-byte aligned, decay_bits 8-byte aligned; ema must not overlap the other four; ema_omd in [0, 1].
+ * A learning-rate schedule needs no entry of its own: the step's rate is passed by value here, to dcf_adam_step and to dcf_amp_update. */
+int dcf_adamw_ema_step(float *params, const float *grads, float *m, float *v, float *ema, const uint64_t *decay_bits, int64_t n,
+                       float lr, float beta1, float beta2, float eps, int step, float gscale, float decay_mul, float ema_omd,
+                       const dcf_amp_state *state, dcf_stream_t stream);
+
 /* dcf_fusion_gather_bwd driven by dcf_fusion_invert's pairs (Cb in {64,128,192,256}): same sums, no idx -> point -> row
  * dependency chain.  The map's pairs are [*e_begin, *e_end) = start[g*(n_max+1)], start[g*(n_max+1)+n_max];
  * max_entries = K*h*w sizes the grid.
