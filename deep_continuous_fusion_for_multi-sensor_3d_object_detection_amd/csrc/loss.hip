@@ -56,7 +56,7 @@ struct SampleMaps {
 };
 
 // reduction 0 = 'last' (reference behaviour: only the last sample counts), 1 = 'sum', 2 = 'mean'
-__device__ __forceinline__ float sample_weight(int reduction, int B) { return reduction == 2 ? 1.f / (float)B : 1.f; }
+__host__ __device__ __forceinline__ float sample_weight(int reduction, int B) { return reduction == 2 ? 1.f / (float)B : 1.f; }
 
 // false for a sample that 'last' leaves out: its workgroup has nothing more to do
 template <bool DET>
@@ -599,6 +599,159 @@ __global__ void __launch_bounds__(256) k_loss_sample_fwd_bwd(LossSampleArgs a)
     sample_terms<DET, 4>(L, m, b, red, a.loss, a.loss_rows);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Dense focal classification ("loss_sampling: focal"): no sampling -- every cell of both anchors enters the
+// classification term, weighted by alpha_t * (1 - p_t)^gamma, normalised by the number of DISTINCT positive cells N_b = max(1, |P_b|);
+// P_b = the cells inside at least one positive window.  The regression rows are those of the sampled modes (every window entry, or the
+// centre cell), through reg_entry above.
+//
+// The grid is (G, B) workgroups over contiguous chunks of the map (hard_chunk: one workgroup for a small map, 35 at cfg2).  One thread
+// owns each cell: it reads the four scores and STORES the four gradients, so the classification half has no atomics and does not
+// need the zero fill.  A workgroup's partial value goes to its own slot of the workspace; k_focal_fold adds the slots in a fixed
+// order in double and rounds once.  Every workgroup stages the sample's windows itself (<= 64 rectangles, <= 1024 entries) and counts
+// |P_b| redundantly -- entry (k, cell) is a first occurrence iff no box k' < k holds the cell, <= 4 entries x 64 rectangles per thread --
+// which costs less than the launch of a pre-kernel the whole grid would have to wait for.
+//
+// per-sample workspace, in floats: [0, G) the workgroups' classification partials (not yet divided by N_b), then
+constexpr int FS_REG = HARD_MAXG;               // the regression term (without the gain)
+constexpr int FS_NPOS = HARD_MAXG + 1;          // |P_b| (an integer below 2^24: exact)
+constexpr int FS_STRIDE = HARD_MAXG + 2;
+
+struct LossFocalArgs {
+    const float *cls, *reg, *anc, *boxes;
+    const int32_t *nbox;
+    int64_t cls_bs, reg_bs, gcls_bs, greg_bs;
+    float *gcls, *greg, *ws;
+    int max_box, box_stride, b0, B, H, W, span, regress_type, reduction, chunk;
+    float xs, xo, ys, yo, rs, gain, alpha, gamma, eps;
+};
+
+// DCF-DET-BEGIN
+// Focal term of one (anchor, cell): adds FL to acc and returns d FL / d p_t, both at q = the clamped probability.  The clamp is a
+// comparison, not fmaxf: a NaN score stays NaN and reaches the guarded optimiser step.  The two gradient terms have one sign.
+__device__ __forceinline__ float focal_cell(float pt, float alpha_t, float gamma, float eps, float &acc)
+{
+    const float q = pt < eps ? eps : pt;
+    const float lnq = logf(q);
+    if (gamma == 0.f) {
+        acc += -alpha_t * lnq;
+        return -alpha_t / q;
+    }
+    const float om = 1.f - q;
+    const float pw1 = powf(om, gamma - 1.f);    // (1 - q)^(gamma - 1); gamma >= 1, so this is finite at q = 1
+    const float pw = pw1 * om;
+    acc += -alpha_t * pw * lnq;
+    return alpha_t * gamma * pw1 * lnq - alpha_t * pw / q;
+}
+// DCF-DET-END
+
+template <bool DET>
+__global__ void __launch_bounds__(HARD_THREADS) k_loss_focal(LossFocalArgs a)
+{
+    __shared__ float red[4];
+    __shared__ int e_cell[LS_MAXE];            // window entry -> cell, in the reference's order (box, dx, dy): the regression rows
+    __shared__ short e_box[LS_MAXE];
+    __shared__ int box_first[65], box_cx[64], box_cy[64];
+    __shared__ int rx0[64], rx1[64], ry0[64], ry1[64];      // the clipped window of box k; x0 > x1 for a box off the grid
+    __shared__ int s_cnt[HARD_THREADS / 64];
+    const int g = blockIdx.x, b = a.b0 + blockIdx.y, tid = threadIdx.x;
+    const int HW = a.H * a.W, half = a.span / 2;
+    const int nb = min(a.nbox[b], a.max_box);
+    const float *bx = a.boxes + (int64_t)b * a.max_box * a.box_stride;
+    if (tid < nb) {
+        // the centre cell exactly as k_loss_sample_fwd_bwd computes it (fp32, one rounding per operation, truncation)
+        const int cx = (int)(__fdiv_rn(__fadd_rn(__fmul_rn(bx[tid * a.box_stride], a.xs), a.xo), a.rs));
+        const int cy = (int)(__fdiv_rn(__fadd_rn(__fmul_rn(bx[tid * a.box_stride + 1], a.ys), a.yo), a.rs));
+        const bool in = !(cx < 0 || cx > a.H - 1 || cy < 0 || cy > a.W - 1);
+        box_cx[tid] = in ? cx : -1000000; box_cy[tid] = cy;
+        rx0[tid] = in ? max(cx - half, 0) : 0; rx1[tid] = in ? min(cx - half + a.span - 1, a.H - 1) : -1;
+        ry0[tid] = in ? max(cy - half, 0) : 0; ry1[tid] = in ? min(cy - half + a.span - 1, a.W - 1) : -1;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int n = 0;
+        for (int k = 0; k < nb; ++k) {
+            box_first[k] = n;
+            n += (rx1[k] - rx0[k] + 1) * (ry1[k] - ry0[k] + 1);      // (0 for a box off the grid)
+        }
+        box_first[nb > 0 ? nb : 0] = n;
+    }
+    __syncthreads();
+    const int np = min(box_first[nb > 0 ? nb : 0], LS_MAXE);          // (the entry checks max_box * span^2 <= LS_MAXE)
+    if (tid < nb) {
+        int n = box_first[tid];
+        for (int px = rx0[tid]; px <= rx1[tid]; ++px)
+            for (int py = ry0[tid]; py <= ry1[tid]; ++py, ++n)
+                if (n < LS_MAXE) { e_cell[n] = px * a.W + py; e_box[n] = (short)tid; }
+    }
+    __syncthreads();
+    // ---- |P_b|: the entries whose cell no earlier box holds (integer work: the same count in every workgroup)
+    int cnt = 0;
+    for (int e = tid; e < np; e += HARD_THREADS) {
+        const int cell = e_cell[e], k = e_box[e];
+        const int px = cell / a.W, py = cell - px * a.W;
+        bool first = true;
+        for (int k2 = 0; k2 < k; ++k2) first &= !(px >= rx0[k2] && px <= rx1[k2] && py >= ry0[k2] && py <= ry1[k2]);
+        cnt += first ? 1 : 0;
+    }
+    cnt = wave_sum_i(cnt);
+    if ((tid & 63) == 0) s_cnt[tid >> 6] = cnt;
+    __syncthreads();
+    const int npos = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+    const float wsample = sample_weight(a.reduction, a.B);
+    const float gscale = (1.f / (float)max(npos, 1)) * wsample;
+    // ---- the classification term of this workgroup's cells
+    const float *c = a.cls + b * a.cls_bs;
+    float *gc = a.gcls + b * a.gcls_bs;
+    const int lo = g * a.chunk, hi = min(lo + a.chunk, HW);
+    float acc = 0.f;
+    // DCF-DET-BEGIN
+    for (int cell = lo + tid; cell < hi; cell += HARD_THREADS) {
+        const int px = cell / a.W, py = cell - px * a.W;
+        bool y = false;
+        for (int k = 0; k < nb; ++k) y |= px >= rx0[k] && px <= rx1[k] && py >= ry0[k] && py <= ry1[k];
+        const float alpha_t = y ? a.alpha : 1.f - a.alpha;
+#pragma unroll
+        for (int an = 0; an < 2; ++an) {
+            const float s0 = c[(int64_t)(2 * an) * HW + cell], s1 = c[(int64_t)(2 * an + 1) * HW + cell];
+            const float gq = focal_cell(y ? s1 : s0, alpha_t, a.gamma, a.eps, acc) * gscale;
+            gc[(int64_t)(2 * an) * HW + cell] = y ? 0.f : gq;
+            gc[(int64_t)(2 * an + 1) * HW + cell] = y ? gq : 0.f;
+        }
+    }
+    const float part = block_sum<4>(acc, red);
+    float *ws = a.ws + (int64_t)b * FS_STRIDE;
+    if (tid == 0) ws[g] = part;
+    // DCF-DET-END
+    if (g != 0) return;
+    // ---- the sample's regression rows, in its workgroup 0
+    const SampledItems L = {nullptr, nullptr, e_cell, e_box, box_first, box_cx, box_cy, bx, a.box_stride, a.regress_type, a.W, 0, 0, np};
+    const SampleMaps m = {c, a.reg + b * a.reg_bs, a.anc, gc, a.greg + b * a.greg_bs, HW, a.gain, wsample};
+    float accr = 0.f;
+    for (int e = tid; e < np * 14; e += HARD_THREADS) reg_entry<DET>(L, m, e, accr);
+    const float regv = block_sum<4>(accr, red);
+    if (tid == 0) { ws[FS_REG] = regv; ws[FS_NPOS] = (float)npos; }
+}
+
+// loss = sum over the samples that count of wsample * (cls_b + gain * reg_b), cls_b = (partials in workgroup order) / N_b: one thread,
+// in double, rounded once; terms [B][3] = (cls_b, reg_b, |P_b|), zero rows for the samples 'last' leaves out
+__global__ void k_focal_fold(const float *ws, int B, int b0, int G, float gain, float wsample, float *loss, float *terms)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double tot = 0.0;
+    for (int b = 0; b < B; ++b) {
+        float *t = terms + 3 * b;
+        if (b < b0) { t[0] = 0.f; t[1] = 0.f; t[2] = 0.f; continue; }
+        const float *w = ws + (int64_t)b * FS_STRIDE;
+        double s = 0.0;
+        for (int g = 0; g < G; ++g) s += (double)w[g];
+        const double clsv = s / (double)fmaxf(w[FS_NPOS], 1.f);
+        t[0] = (float)clsv; t[1] = w[FS_REG]; t[2] = w[FS_NPOS];
+        tot += (double)wsample * (clsv + (double)gain * (double)w[FS_REG]);
+    }
+    *loss = (float)tot;
+}
+
 }  // namespace
 
 extern "C" uint32_t dcf_loss_sample_rand(uint64_t seed, int sample, int stream, int index, int attempt)
@@ -720,6 +873,71 @@ extern "C" int dcf_loss_hard_fwd_bwd_det(const float *cls, int64_t cls_bstride, 
     return loss_sample_impl("dcf_loss_hard_fwd_bwd_det", true, workspace, loss_rows, cls, cls_bstride, reg, reg_bstride, anchors, boxes, nbox_dev, max_box,
                             box_stride, B, H, W, xs, xo, ys, yo, reduced_scale, span, regress_type, pos_cap, neg_count, seed, reg_gain, reduction, loss,
                             gcls, gcls_bstride, greg, greg_bstride, pos_out, neg_out, counts_out, stream);
+}
+
+// loss_sampling: focal (k_loss_focal over the whole map, then the fold)
+extern "C" size_t dcf_loss_focal_workspace_bytes(int B, int H, int W)
+{
+    if (B <= 0 || H <= 0 || W <= 0 || (int64_t)H * W >= (int64_t)1 << 30) return 0;
+    return (size_t)B * FS_STRIDE * sizeof(float);
+}
+
+static int loss_focal_impl(const char *who, bool det, const float *cls, int64_t cls_bstride, const float *reg, int64_t reg_bstride, const float *anchors,
+                           const float *boxes, const int32_t *nbox_dev, int max_box, int box_stride, int B, int H, int W, float xs, float xo,
+                           float ys, float yo, float reduced_scale, int span, int regress_type, float alpha, float gamma, float eps,
+                           float reg_gain, int reduction, float *loss, float *gcls, int64_t gcls_bstride, float *greg, int64_t greg_bstride,
+                           float *terms, void *workspace, dcf_stream_t stream)
+{
+    DCF_REQUIRE(cls && reg && anchors && boxes && nbox_dev && loss && gcls && greg && terms && B > 0 && H > 0 && W > 0, "%s: bad arguments", who);
+    DCF_REQUIRE(reduction >= 0 && reduction <= 2, "%s: reduction must be 0 (last), 1 (sum) or 2 (mean)", who);
+    DCF_REQUIRE(max_box >= 0 && max_box <= 64 && span >= 1 && max_box * span * span <= LS_MAXE && box_stride >= 7,
+                "%s: at most 64 boxes and %d window cells per sample", who, LS_MAXE);
+    DCF_REQUIRE((int64_t)H * W < (int64_t)1 << 30, "%s: map too large", who);
+    DCF_REQUIRE(alpha > 0.f && alpha < 1.f && (gamma == 0.f || gamma >= 1.f) && eps > 0.f && eps <= 1e-3f,
+                "%s: alpha in (0, 1), gamma 0 or >= 1, eps in (0, 1e-3]", who);
+    DCF_REQUIRE(workspace && ((uintptr_t)workspace & 3) == 0, "%s: null or misaligned workspace", who);
+    const int HW = H * W;
+    LossFocalArgs a;
+    a.cls = cls; a.reg = reg; a.anc = anchors; a.boxes = boxes; a.nbox = nbox_dev;
+    a.cls_bs = cls_bstride; a.reg_bs = reg_bstride; a.gcls_bs = gcls_bstride; a.greg_bs = greg_bstride;
+    a.gcls = gcls; a.greg = greg; a.ws = (float *)workspace;
+    a.max_box = max_box; a.box_stride = box_stride; a.B = B; a.H = H; a.W = W; a.span = span; a.regress_type = regress_type;
+    a.reduction = reduction; a.chunk = hard_chunk(HW);
+    a.b0 = reduction == 0 ? B - 1 : 0;              // 'last': only the last sample is computed
+    a.xs = xs; a.xo = xo; a.ys = ys; a.yo = yo; a.rs = reduced_scale; a.gain = reg_gain; a.alpha = alpha; a.gamma = gamma; a.eps = eps;
+    const int G = cdiv(HW, a.chunk);
+    const dim3 grid(G, B - a.b0);
+    const double map_bytes = (double)(B - a.b0) * HW * 4.0;
+    hipStream_t s = S(stream);
+    if (det)
+        DCF_LAUNCH_B("loss_focal_fwd_bwd_det", 8.0 * map_bytes, s, hipLaunchKernelGGL(k_loss_focal<true>, grid, dim3(HARD_THREADS), 0, s, a));
+    else
+        DCF_LAUNCH_B("loss_focal_fwd_bwd", 8.0 * map_bytes, s, hipLaunchKernelGGL(k_loss_focal<false>, grid, dim3(HARD_THREADS), 0, s, a));
+    DCF_LAUNCH("loss_focal_fold", s, hipLaunchKernelGGL(k_focal_fold, dim3(1), dim3(64), 0, s, a.ws, B, a.b0, G, reg_gain, sample_weight(reduction, B), loss, terms));
+    return DCF_OK;
+}
+
+extern "C" int dcf_loss_focal_fwd_bwd(const float *cls, int64_t cls_bstride, const float *reg, int64_t reg_bstride, const float *anchors,
+                                      const float *boxes, const int32_t *nbox_dev, int max_box, int box_stride, int B, int H, int W,
+                                      float xs, float xo, float ys, float yo, float reduced_scale, int span, int regress_type, float alpha,
+                                      float gamma, float eps, float reg_gain, int reduction, float *loss, float *gcls, int64_t gcls_bstride,
+                                      float *greg, int64_t greg_bstride, float *terms, void *workspace, dcf_stream_t stream)
+{
+    return loss_focal_impl("dcf_loss_focal_fwd_bwd", false, cls, cls_bstride, reg, reg_bstride, anchors, boxes, nbox_dev, max_box, box_stride, B, H, W, xs,
+                           xo, ys, yo, reduced_scale, span, regress_type, alpha, gamma, eps, reg_gain, reduction, loss, gcls, gcls_bstride, greg,
+                           greg_bstride, terms, workspace, stream);
+}
+
+// The same launch with the regression gradients summed in one fixed order (deterministic: true); everything else is already fixed.
+extern "C" int dcf_loss_focal_fwd_bwd_det(const float *cls, int64_t cls_bstride, const float *reg, int64_t reg_bstride, const float *anchors,
+                                          const float *boxes, const int32_t *nbox_dev, int max_box, int box_stride, int B, int H, int W,
+                                          float xs, float xo, float ys, float yo, float reduced_scale, int span, int regress_type, float alpha,
+                                          float gamma, float eps, float reg_gain, int reduction, float *loss, float *gcls, int64_t gcls_bstride,
+                                          float *greg, int64_t greg_bstride, float *terms, void *workspace, dcf_stream_t stream)
+{
+    return loss_focal_impl("dcf_loss_focal_fwd_bwd_det", true, cls, cls_bstride, reg, reg_bstride, anchors, boxes, nbox_dev, max_box, box_stride, B, H, W,
+                           xs, xo, ys, yo, reduced_scale, span, regress_type, alpha, gamma, eps, reg_gain, reduction, loss, gcls, gcls_bstride, greg,
+                           greg_bstride, terms, workspace, stream);
 }
 
 extern "C" int dcf_loss_fwd_bwd_det(const float *cls, int64_t cls_bstride, const float *reg, int64_t reg_bstride, const float *anchors,

@@ -16,6 +16,11 @@ instead of numpy's generator) -- no host loop, no index lists over PCIe; `compat
 top-k over the score map, csrc/loss.hip k_hard_*; no randomness in the negatives).  hard_negatives() below is the host statement
 of that selection; CPU tensors take it, so the mode also runs without a device.
 
+`loss_sampling: focal` samples nothing: every cell of both anchors enters the classification term, weighted by the focal factor
+alpha_t * (1 - p_t)^gamma and normalised by the number of distinct positive cells (csrc/loss.hip, k_loss_focal: one pass over the score
+map, one thread per cell, no atomics in the classification half); the regression rows are those of the other modes.  focal_terms() below
+is the host statement (float64); CPU tensors take it.  LossTotal.last_terms then holds (cls_b, reg_b, |P_b|) per sample.
+
 Reference quirks are kept behind `loss_reduction: last` (default): cross-entropy on already
 soft-maxed scores (loss.py:17-20,139), 129 negatives (:125), only the last sample of the
 batch contributes (:71).  'sum' / 'mean' accumulate over the batch instead.
@@ -120,6 +125,54 @@ def hard_negatives(cls_sample, window_cells, neg_count):
     return cells[order[:neg_count]].astype(np.int64)
 
 
+def parse_focal_config(config):
+    """(focal_alpha, focal_gamma, focal_eps) of `loss_sampling: focal`, validated: alpha in (0, 1); gamma 0 or >= 1 (in between,
+    (1-p)^(gamma-1) of the gradient is unbounded at p = 1); eps in (0, 1e-3]."""
+    alpha, gamma, eps = (config.get("focal_alpha", 0.25), config.get("focal_gamma", 2.0), config.get("focal_eps", 1e-12))
+    for key, v in (("focal_alpha", alpha), ("focal_gamma", gamma), ("focal_eps", eps)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not np.isfinite(v):
+            raise ValueError("%s must be a finite number (got %r)" % (key, v))
+    if not 0.0 < alpha < 1.0:
+        raise ValueError("focal_alpha must lie in (0, 1) (got %r)" % (alpha,))
+    if not (gamma == 0 or gamma >= 1.0):
+        raise ValueError("focal_gamma must be 0 or >= 1 (got %r)" % (gamma,))
+    if not 0.0 < eps <= 1e-3:
+        raise ValueError("focal_eps must lie in (0, 1e-3] (got %r)" % (eps,))
+    return float(alpha), float(gamma), float(eps)
+
+
+def focal_terms(cls_b, P_b, alpha, gamma, eps):
+    """The host statement of the focal classification term of one sample, in float64: cls_b [4, HW] scores, P_b = the positive
+    cells -> (value, gradient [4, HW]).  For anchor a and cell i with y = (i in P_b): p_t = cls_b[2a+y, i], alpha_t = alpha if y else
+    1 - alpha, q = eps where p_t < eps else p_t (a NaN stays NaN), FL = -alpha_t (1-q)^gamma ln q; value = sum FL / max(1, |P_b|).
+    The gradient is taken at q, also where the clamp acted; the other channel of the pair gets 0."""
+    c = np.asarray(cls_b, dtype=np.float64)
+    HW = c.shape[1]
+    y = np.zeros(HW, dtype=bool)
+    cells = sorted(set(int(v) for v in P_b))
+    if cells:
+        y[np.array(cells, dtype=np.int64)] = True
+    inv_n = 1.0 / max(1, len(cells))
+    alpha_t = np.where(y, alpha, 1.0 - alpha)
+    grad = np.zeros((4, HW), dtype=np.float64)
+    value = 0.0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for a in range(2):
+            pt = np.where(y, c[2 * a + 1], c[2 * a])
+            q = np.where(pt < eps, eps, pt)
+            lnq = np.log(q)
+            if gamma == 0:
+                fl, g = -alpha_t * lnq, -alpha_t / q
+            else:
+                om = 1.0 - q
+                fl = -alpha_t * om ** gamma * lnq
+                g = alpha_t * gamma * om ** (gamma - 1.0) * lnq - alpha_t * om ** gamma / q
+            value += fl.sum()
+            grad[2 * a + 1] = np.where(y, g, 0.0) * inv_n
+            grad[2 * a] = np.where(y, 0.0, g) * inv_n
+    return value * inv_n, grad
+
+
 class LossTotal(nn.Module):
     def __init__(self, config):
         super(LossTotal, self).__init__()
@@ -127,8 +180,10 @@ class LossTotal(nn.Module):
         self.regress_type = config["regress_type"]
         self.reduction = config.get("loss_reduction", "last")
         self.sampling = config.get("loss_sampling", "compat")
-        if self.sampling not in ("compat", "device", "hard"):
-            raise ValueError("loss_sampling must be compat, device or hard (got %r)" % (self.sampling,))
+        if self.sampling not in ("compat", "device", "hard", "focal"):
+            raise ValueError("loss_sampling must be compat, device, hard or focal (got %r)" % (self.sampling,))
+        self.focal = parse_focal_config(config) if self.sampling == "focal" else None      # (alpha, gamma, eps)
+        self.last_terms = None             # focal: [B,3] fp32 = (cls_b, reg_b without the gain, |P_b|) of the last call, unweighted
         from .model import parse_deterministic_config
         self.deterministic = parse_deterministic_config(config)      # both device entries then sum in one fixed order (csrc/loss.hip, DET)
         self.seed = int(config.get("loss_seed", 0))
@@ -330,10 +385,8 @@ class LossTotal(nn.Module):
             base = None
         return base, cls, reg
 
-    def _forward_device_sampling(self, boxes, nbox, cls, reg, anc, B, H, W):
-        c = self.config
-        dev = cls.device
-        # labels: [B,max,9] fp32 and the counts, one small asynchronous copy each when they arrive on the host
+    def _stage_labels(self, boxes, nbox, dev):
+        """The labels on the device: [B,max,9] fp32 and the counts (int32), one small asynchronous copy each when they arrive on the host."""
         if not boxes.is_cuda:
             ring = getattr(self, "_box_ring", None)
             if ring is None or ring[0][0].shape != boxes.shape:
@@ -350,6 +403,12 @@ class LossTotal(nn.Module):
         else:
             boxes = boxes.float().contiguous()
         nb = nbox.to(device=dev, dtype=torch.int32, non_blocking=True) if torch.is_tensor(nbox) else torch.tensor([int(v) for v in nbox], dtype=torch.int32, device=dev)
+        return boxes, nb
+
+    def _forward_device_sampling(self, boxes, nbox, cls, reg, anc, B, H, W):
+        c = self.config
+        dev = cls.device
+        boxes, nb = self._stage_labels(boxes, nbox, dev)
         base, cls, reg = self._head_views(cls, reg, H, W)
         span, pos_cap, neg_count = c["positive_range"], c["pos_sample_threshold"], c["neg_sample_threshold"] + 1
         rs, gain, red = c["anchor_bbox_feature"]["reduced_scale"], c["regress_loss_gain"], REDUCTION[self.reduction]
@@ -411,6 +470,63 @@ class LossTotal(nn.Module):
             self.last_samples = (pos_t, neg_t, counts)
         return self._forward_lists(cls, reg, anc, samples, B, H, W)
 
+    def _forward_focal(self, boxes, nbox, cls, reg, anc, B, H, W):
+        """loss_sampling: focal.  CUDA tensors: one launch of dcf_loss_focal_fwd_bwd(_det).  CPU tensors: the host statement
+        (focal_terms + the torch regression term) behind the same autograd function.  Nothing is drawn: calls is not advanced."""
+        c = self.config
+        dev = cls.device
+        alpha, gamma, eps = self.focal
+        gain, red = float(c["regress_loss_gain"]), REDUCTION[self.reduction]
+        ws = getattr(self, "_focal_ws", None)           # scratch and terms: allocated once per map shape
+        if dev.type != "cuda":
+            boxes_host = boxes.detach().float()
+            if ws is None or ws[0] != (B, H, W, dev):
+                ws = self._focal_ws = ((B, H, W, dev), None, torch.zeros((B, 3), dtype=torch.float32))
+            self.last_terms = terms = ws[2]
+
+            def launch(loss, gcls, greg):
+                self._focal_host(boxes_host, nbox, cls.detach(), reg.detach(), anc, B, H, W, loss, gcls, greg, terms)
+            return _FusedLoss.apply(None, cls, reg, launch)
+        from . import ops
+        boxes, nb = self._stage_labels(boxes, nbox, dev)
+        base, cls, reg = self._head_views(cls, reg, H, W)
+        if ws is None or ws[0] != (B, H, W, dev):
+            ws = self._focal_ws = ((B, H, W, dev),) + ops.loss_focal_workspace(B, H, W, dev)
+        self.last_terms = terms = ws[2]
+        grid = (self._xs, self._xo, self._ys, self._yo, c["anchor_bbox_feature"]["reduced_scale"])
+
+        def launch(loss, gcls, greg):
+            ops.loss_focal(cls, reg, anc, boxes, nb, grid, c["positive_range"], self.regress_type, alpha, gamma, eps, gain, red,
+                           loss, gcls, greg, terms, ws[1], deterministic=self.deterministic)
+        return _FusedLoss.apply(base, cls, reg, launch)
+
+    def _focal_host(self, boxes_host, nbox, cls, reg, anc, B, H, W, loss, gcls, greg, terms):
+        """The host statement of the focal entry: fills loss [1], the gradient maps and terms [B,3] (float64 arithmetic for the
+        classification term, the torch regression term of the other modes and its autograd gradient)."""
+        alpha, gamma, eps = self.focal
+        gain = float(self.config["regress_loss_gain"])
+        bh = boxes_host.numpy()
+        terms.zero_()
+        total = 0.0
+        counted = [B - 1] if self.reduction == "last" else list(range(B))
+        w = 1.0 / B if self.reduction == "mean" else 1.0
+        for b in counted:
+            nb = max(min(int(nbox[b]), bh.shape[1]), 0)
+            cells, rows, row_box, row_w = self.windows(bh[b, :nb], H, W)
+            value, grad = focal_terms(cls[b].reshape(4, H * W).double().numpy(), cells, alpha, gamma, eps)
+            gcls[b] = torch.from_numpy(grad * w).to(gcls.dtype).reshape(4, H, W)
+            lr = 0.0
+            if rows:
+                with torch.enable_grad():
+                    rb = reg[b].clone().requires_grad_(True)
+                    term = self._reg_term(rb, anc, torch.tensor(rows, dtype=torch.long), torch.tensor(row_box, dtype=torch.long),
+                                          torch.tensor(row_w, dtype=torch.float32), torch.from_numpy(bh[b, :nb, :7]), H, W)
+                    greg[b] = torch.autograd.grad(term, rb)[0] * (gain * w)
+                lr = term.item()
+            terms[b] = torch.tensor([value, lr, len(set(cells))], dtype=torch.float32)
+            total += w * (value + gain * lr)
+        loss[0] = total
+
     def forward(self, reference_bboxes_batch, num_ref_bbox_batch, predicted_class_feature_batch, predicted_regress_feature_batch):
         cls, reg = predicted_class_feature_batch, predicted_regress_feature_batch
         dev = cls.device
@@ -419,6 +535,8 @@ class LossTotal(nn.Module):
         if getattr(self, "_anc_dev", None) is None or self._anc_dev.device != dev:
             self._anc_dev = self.anchor_set.to(dev).reshape(2, 7, H * W)
         anc = self._anc_dev
+        if self.sampling == "focal":
+            return self._forward_focal(reference_bboxes_batch, num_ref_bbox_batch, cls, reg, anc, B, H, W)
         if self.sampling == "device" or (self.sampling == "hard" and dev.type == "cuda"):
             if dev.type != "cuda":
                 raise RuntimeError("loss_sampling: device needs CUDA tensors (the host path is loss_sampling: compat)")
@@ -442,6 +560,21 @@ class LossTotal(nn.Module):
                     row_w.append(1.0 / (len(owner[k]) * 14))
             samples.append(([p[0] * W + p[1] for p in pos], [q[0] * W + q[1] for q in neg], rows, row_box, row_w, boxes_host[b, :nb, :7].numpy()))
         return self._forward_lists(cls, reg, anc, samples, B, H, W)
+
+    @staticmethod
+    def _reg_term(reg_b, anc, rows, rbox, w_row, boxes, H, W):
+        """Smooth-L1 of the encoded box offsets of one sample as torch ops: reg_b [14,h,w], rows / rbox the regression cells and the
+        box of each, w_row their weights, boxes [nbox,7]."""
+        nrow = rows.shape[0]
+        pred = reg_b.reshape(14, H * W)[:, rows].t().reshape(nrow, 2, 7)
+        an = anc[:, :, rows].permute(2, 0, 1)            # [nrow,2,7]
+        ref = boxes[rbox].unsqueeze(1)                   # [nrow,1,7]
+        diag = torch.sqrt(an[:, :, 3:4] ** 2 + an[:, :, 4:5] ** 2)
+        d = ref[:, :, 6] - an[:, :, 6]
+        target = torch.cat(((ref[:, :, 0:2] - an[:, :, 0:2]) / diag, (ref[:, :, 2:3] - an[:, :, 2:3]) / an[:, :, 5:6],
+                            torch.log(ref[:, :, 3:6] / an[:, :, 3:6]), torch.atan2(torch.sin(d), torch.cos(d)).unsqueeze(-1)), -1)
+        per_row = F.smooth_l1_loss(pred, target, reduction="none").sum((1, 2))
+        return (per_row * w_row).sum()                   # = sum over boxes of the per-box mean (loss.py:163,186)
 
     def _terms_host(self, cls, reg, anc, di, df, B, H, W):
         """The terms on the packed lists as torch ops (CPU tensors): gathers + CE + Smooth-L1, vectorised per sample."""
@@ -469,15 +602,7 @@ class LossTotal(nn.Module):
                 rbox = di[o + npos + nneg + nrow:o + npos + nneg + 2 * nrow]
                 w_row = df[of:of + nrow]
                 boxes = df[of + nrow:of + nrow + nb * 7].reshape(nb, 7)
-                pred = reg[b].reshape(14, H * W)[:, rows].t().reshape(nrow, 2, 7)
-                an = anc[:, :, rows].permute(2, 0, 1)            # [nrow,2,7]
-                ref = boxes[rbox].unsqueeze(1)                   # [nrow,1,7]
-                diag = torch.sqrt(an[:, :, 3:4] ** 2 + an[:, :, 4:5] ** 2)
-                d = ref[:, :, 6] - an[:, :, 6]
-                target = torch.cat(((ref[:, :, 0:2] - an[:, :, 0:2]) / diag, (ref[:, :, 2:3] - an[:, :, 2:3]) / an[:, :, 5:6],
-                                    torch.log(ref[:, :, 3:6] / an[:, :, 3:6]), torch.atan2(torch.sin(d), torch.cos(d)).unsqueeze(-1)), -1)
-                per_row = F.smooth_l1_loss(pred, target, reduction="none").sum((1, 2))
-                lr = lr + (per_row * w_row).sum()                # = sum over boxes of the per-box mean (loss.py:163,186)
+                lr = lr + self._reg_term(reg[b], anc, rows, rbox, w_row, boxes, H, W)
             total = lc + self.config["regress_loss_gain"] * lr
             acc = acc + total
         if self.reduction == "last":

@@ -902,3 +902,26 @@ def eval_ap(acc_scores, acc_tpmask, state, nthr):
     ws = torch.empty((H.lib().dcf_eval_ap_workspace_bytes(cap),), dtype=torch.uint8, device=acc_scores.device)
     H.call("dcf_eval_ap", _chk(acc_scores, "acc_scores"), _chk(acc_tpmask, "acc_tpmask"), _chk(state, "state"), cap, nthr, ap, tp, ws, H.stream_ptr())
     return ap, tp
+
+
+# ------------------------------------------------------------------ dense focal classification loss (loss_sampling: focal)
+def loss_focal_workspace(B, Hh, W, device):
+    """(workspace, terms [B,3]) of loss_focal for one map shape; contents free between calls on one stream."""
+    nbytes = H.lib().dcf_loss_focal_workspace_bytes(B, Hh, W)
+    if nbytes == 0:
+        raise H.DcfError("loss_focal: bad map shape %r" % ((B, Hh, W),))
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device), torch.zeros((B, 3), dtype=torch.float32, device=device)
+
+
+def loss_focal(cls, reg, anchors, boxes, nbox, grid, span, regress_type, alpha, gamma, eps, gain, reduction, loss, gcls, greg, terms, ws,
+               deterministic=False):
+    """One launch of the focal objective and its gradients.  cls [B,4,h,w] / reg [B,14,h,w] fp32 views with unit cell stride, anchors
+    [2,7,h*w], boxes [B,max,>=7] fp32 and nbox int32 [B] on the device, grid = (xs, xo, ys, yo, reduced_scale); loss [1], gcls / greg
+    (greg zeroed) and terms [B,3] are written.  reduction: 0 last, 1 sum, 2 mean."""
+    B, _, Hh, W = cls.shape
+    xs, xo, ys, yo, rs = [float(v) for v in grid]
+    H.call("dcf_loss_focal_fwd_bwd_det" if deterministic else "dcf_loss_focal_fwd_bwd", cls, cls.stride(0), reg,
+           reg.stride(0), anchors, _chk(boxes, "boxes"), nbox, boxes.shape[1], boxes.shape[2], B, Hh, W, xs, xo, ys, yo, rs, int(span),
+           int(regress_type), float(alpha), float(gamma), float(eps), float(gain), int(reduction), loss, gcls, gcls.stride(0), greg,
+           greg.stride(0), terms, ws, H.stream_ptr())
+    return loss

@@ -585,6 +585,13 @@ class Train(nn.Module):
         """Global L2 norm of the last step's averaged, unscaled gradient (device tensor, a copy; before clipping)."""
         return None if self.optimizer.amp is None else self.optimizer.amp.grad_norm.clone()
 
+    def loss_terms(self):
+        """loss_sampling: focal -- [B,3] fp32 = (classification term, regression term without the gain, positive cells) per sample of
+        the last step, unweighted; zero rows for the samples `loss_reduction: last` leaves out (device tensor, a copy).  None in the
+        other modes."""
+        terms = self.loss_total.last_terms
+        return None if terms is None else terms.clone()
+
     def skipped_steps(self):
         """Steps skipped for a non-finite gradient so far (device int64 tensor, a copy)."""
         return None if self.optimizer.amp is None else self.optimizer.amp.skipped_steps.clone()
@@ -807,8 +814,14 @@ def main():
             if training.ema_params() is not None:                          # the averaged weights beside the model, same key names
                 torch.save(training.ema_state_dict(), "./saved_model/" + config["saved_model_name"] + "_ema")
             print("epoch %d: learning rate %.6g" % (epoch, training.learning_rate()))
+        terms_sum, terms_n = None, 0                                       # focal: the epoch's mean terms, added up on the device
         for batch_ndx, batch in enumerate(loader):
             training.one_step_raw(dataset.geometry, batch)
+            terms = training.loss_terms()
+            if terms is not None:                                          # (the batch mean is over the samples the reduction counts)
+                counted = terms[-1:] if training.loss_total.reduction == "last" else terms
+                terms_sum = counted.mean(0) if terms_sum is None else terms_sum + counted.mean(0)
+                terms_n += 1
             if batch_ndx % 100 == 0:
                 print("training at ", batch_ndx, "is processed, loss %.4f" % training.loss_value.item())
             if batch_ndx % 500 == 0 and batch_ndx != 0:                    # train.py:87-100
@@ -821,6 +834,9 @@ def main():
                     print("batch %d: validation loss %.4f, positives %d, labelled %d, TP@0.5 %d" % (batch_ndx, mean, npos, nt, tp[0.5]))
                     _print_ranked(tester)
                 _eval_barrier()
+        if rank0 and terms_n:
+            cls_mean, reg_mean, npos_mean = (terms_sum / terms_n).tolist()
+            print("epoch %d: focal classification %.4f, regression %.4f, positive cells %.1f (batch means)" % (epoch, cls_mean, reg_mean, npos_mean))
         _eval_barrier()
         if rank0:                                                          # train.py:105-122
             mean, cum, npos, nt, tp = evaluate(training, tester, test_dataset, test_loader, max_batches=int(config.get("eval_batches_epoch", 12)))   # `batch_ndx > 10`

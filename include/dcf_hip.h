@@ -594,6 +594,31 @@ int dcf_loss_hard_fwd_bwd_det(const float *cls, int64_t cls_bstride, const float
                               int64_t gcls_bstride, float *greg, int64_t greg_bstride, int32_t *pos_out, int32_t *neg_out,
                               int32_t *counts_out, void *workspace, float *loss_rows, dcf_stream_t stream);
 
+/* (version 202 still: added without a new minor) Dense focal classification (`loss_sampling: focal`): no
+ * sampling.  P_b = the DISTINCT cells inside at least one positive window of sample b (windows as above), N_b = max(1, |P_b|).  For
+ * anchor a and cell i, y = (i in P_b): p_t = cls[2a+y][i], alpha_t = y ? alpha : 1 - alpha, q = p_t < eps ? eps : p_t (a comparison:
+ * a NaN score stays NaN), FL = -alpha_t (1-q)^gamma ln q, cls_b = sum FL / N_b; the gradient is taken at q,
+ *     d cls_b / d cls[2a+y][i] = (alpha_t gamma (1-q)^(gamma-1) ln q - alpha_t (1-q)^gamma / q) / N_b        (gamma == 0: -alpha_t / (q N_b)),
+ * and the other channel of the pair gets 0.  Every cell of a computed sample's four gcls channels is STORED (no atomics, no need for
+ * the zero fill); greg receives the regression rows of the sampled modes (every window entry for regress_type 0, else the centre
+ * cell) and must be zeroed.  total_b = cls_b + reg_gain * reg_b; *loss is stored, not added to: the workgroups' partial values are
+ * added in a fixed order in double and rounded once, in both entries.  reduction 0 computes the last sample only.
+ * terms fp32 [B][3] = (cls_b, reg_b without the gain, |P_b|), unweighted; zero rows for samples that reduction 0 leaves out.
+ * alpha in (0, 1), gamma 0 or >= 1, eps in (0, 1e-3]; max_box <= 64, max_box * span^2 <= 1024, H*W < 2^30.
+ * workspace: dcf_loss_focal_workspace_bytes(B, H, W) bytes, 4-byte aligned, contents free on entry; calls that share it must be
+ * ordered on one stream.  The _det entry differs in the regression gradients only: summed per cell in row order instead of atomics. */
+size_t dcf_loss_focal_workspace_bytes(int B, int H, int W);
+int dcf_loss_focal_fwd_bwd(const float *cls, int64_t cls_bstride, const float *reg, int64_t reg_bstride, const float *anchors,
+                           const float *boxes, const int32_t *nbox_dev, int max_box, int box_stride, int B, int H, int W,
+                           float xs, float xo, float ys, float yo, float reduced_scale, int span, int regress_type, float alpha,
+                           float gamma, float eps, float reg_gain, int reduction, float *loss, float *gcls, int64_t gcls_bstride,
+                           float *greg, int64_t greg_bstride, float *terms, void *workspace, dcf_stream_t stream);
+int dcf_loss_focal_fwd_bwd_det(const float *cls, int64_t cls_bstride, const float *reg, int64_t reg_bstride, const float *anchors,
+                               const float *boxes, const int32_t *nbox_dev, int max_box, int box_stride, int B, int H, int W,
+                               float xs, float xo, float ys, float yo, float reduced_scale, int span, int regress_type, float alpha,
+                               float gamma, float eps, float reg_gain, int reduction, float *loss, float *gcls, int64_t gcls_bstride,
+                               float *greg, int64_t greg_bstride, float *terms, void *workspace, dcf_stream_t stream);
+
 /* ------------------------------------------------- evaluation post-processing
  * What /root/reference/test.py:88-206 does on the host, box by box.
  * dcf_eval_score_filter: test.py:88-108.  pred [B][32][h][w] fp32 (the model output: scores in channels 2a+1, decoded boxes in
