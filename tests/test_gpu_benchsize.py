@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from _fusion_ref import fusion_bwd_statement, tap_weights
 from _util import golden_cfg, load_golden, pkg
 from oracle import geometry_ref, model_ref
 
@@ -26,40 +27,6 @@ def _cfg2_frame(seed=5, npts=100000):
     pts = det.synthetic_points(npts, (0.0, 70.4, -40.0, 40.0, -2.4, 0.8), seed=seed)
     _, pc, uv, n, _ = geometry_ref.voxelization_projection(pts, cfg, calib.kitti_like_crt(), proj_mode="correct")
     return ops.GridSpec(cfg), np.ascontiguousarray(pc), np.ascontiguousarray(uv), int(n)
-
-
-def fusion_bwd_statement(P, xyz, idx, stride, aff, w1d, b1, ghs, eps=1e-5):
-    """dP [rows,Cb], dW1d [Cb,3], db1 [Cb] of  hsum[p] = sum_k relu(P[idx_k] + W1d.(dx,dy,z) + b1)  for upstream gradient
-    ghs [h,w,Cb], in fp64 (inputs as given), plus the per-output weight of the terms whose ReLU argument is within eps of 0."""
-    K, h, w = idx.shape
-    rows, Cb = P.shape
-    xs, xo, ys, yo = [np.float32(v) for v in aff[:4]]
-    X = ((np.arange(h, dtype=np.float32) + np.float32(0.5)) * np.float32(stride) - xo) / xs          # fp32, as the device forms it
-    Y = ((np.arange(w, dtype=np.float32) + np.float32(0.5)) * np.float32(stride) - yo) / ys
-    P64, g64 = P.double(), ghs.reshape(h * w, Cb).double()
-    w64, b64 = w1d.double(), b1.double()
-    Xp = torch.from_numpy(X).repeat_interleave(w)
-    Yp = torch.from_numpy(Y).repeat(h)
-    dP, sP = torch.zeros(rows, Cb, dtype=torch.float64), torch.zeros(rows, Cb, dtype=torch.float64)
-    dW, sW = torch.zeros(Cb, 3, dtype=torch.float64), torch.zeros(Cb, 3, dtype=torch.float64)
-    db, sb = torch.zeros(Cb, dtype=torch.float64), torch.zeros(Cb, dtype=torch.float64)
-    for k in range(K):
-        ids = idx[k].reshape(-1).long()
-        valid = ids >= 0
-        safe = ids.clamp(min=0)
-        d = torch.stack(((xyz[safe, 0] - Xp), (xyz[safe, 1] - Yp), xyz[safe, 2]), 1).double()          # fp32 differences, exact in fp64
-        pre = P64[safe] + d @ w64.t() + b64
-        m = (pre > 0) & valid[:, None]
-        amb = (pre.abs() <= eps) & valid[:, None]
-        g = g64 * m
-        ga = g64.abs() * amb
-        dP.index_add_(0, safe, g)
-        sP.index_add_(0, safe, ga)
-        dW += g.t() @ d
-        sW += ga.t() @ d.abs()
-        db += g.sum(0)
-        sb += ga.sum(0)
-    return (dP, dW, db), (sP, sW, sb)
 
 
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
@@ -142,20 +109,14 @@ def test_point_sample_backward_at_cfg2_size(dtype):
     ops.point_sample_bwd(code, gfp.cuda(), uvt.cuda(), cnt, rows, gF)
     fp = ops.point_sample_fwd(code, fmap.cuda(), uvt.cuda(), cnt, rows)
     # fp64 statement (oracle/model_ref.bilinear_sample's taps and weights; weights formed in fp32 like the device)
-    u, v = uvt[:n, 0], uvt[:n, 1]
-    ix, iy = u * 0.25 - 0.5, v * 0.25 - 0.5
-    x0f, y0f = torch.floor(ix), torch.floor(iy)
-    wx, wy = (ix - x0f).double(), (iy - y0f).double()
-    x0, y0 = x0f.long(), y0f.long()
-    x1, y1 = (x0 + 1).clamp(0, Wf - 1), (y0 + 1).clamp(0, Hf - 1)
-    x0, y0 = x0.clamp(0, Wf - 1), y0.clamp(0, Hf - 1)
+    pix, wts = tap_weights(uv[:n], Hf, Wf)
     want = torch.zeros(Hf * Wf, Cf, dtype=torch.float64)
     g64 = gfp[:n].double()
     ref_fp = torch.zeros(n, Cf, dtype=torch.float64)
     f64 = fmap.double().reshape(Hf * Wf, Cf)
-    for yy, xx, ww in ((y0, x0, (1 - wy) * (1 - wx)), (y0, x1, (1 - wy) * wx), (y1, x0, wy * (1 - wx)), (y1, x1, wy * wx)):
-        want.index_add_(0, yy * Wf + xx, g64 * ww[:, None])
-        ref_fp += f64[yy * Wf + xx] * ww[:, None]
+    for t in range(4):
+        want.index_add_(0, pix[:, t], g64 * wts[:, t, None])
+        ref_fp += f64[pix[:, t]] * wts[:, t, None]
     got = gF.cpu().double().reshape(Hf * Wf, Cf)
     assert float((got - want).abs().max()) <= 2e-5 * float(want.abs().max())
     assert float(gF.abs().sum()) > 0

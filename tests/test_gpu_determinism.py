@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+from _fusion_ref import _sorted_pairs, cam_map_statement, fusion_bwd_statement, tap_weights, taps_statement   # noqa: F401
 from _util import pkg
 
 pytestmark = pytest.mark.gpu
@@ -42,45 +43,6 @@ def _knn_case(case, K, h, w, stride, n_max, seed=7):
     cnt = torch.tensor([n], dtype=torch.int32, device="cuda")
     idx = ops.knn_bev(xyz, cnt, K, h, w, stride, AFF)
     return xyz, cnt, idx, n, g
-
-
-def _sorted_pairs(idx, n_max):
-    """numpy statement of the canonical inverse map of ONE KNN map [K,h,w]: (start [n_max+1], ent_pix, ent_pt)."""
-    K, h, w = idx.shape
-    ii, jj = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
-    pix = np.broadcast_to(((ii << 16) | jj)[None], (K, h, w)).reshape(-1)
-    pt = idx.reshape(-1)
-    keep = pt >= 0
-    pix, pt = pix[keep], pt[keep]
-    order = np.lexsort((pix, pt))                           # by point, then by pixel key
-    start = np.concatenate([[0], np.cumsum(np.bincount(pt, minlength=n_max + 1))])[:n_max + 1]
-    return start.astype(np.int32), pix[order].astype(np.int32), pt[order].astype(np.int32)
-
-
-def taps_statement(uv, Hf, Wf):
-    """make_taps' integer taps in numpy (fp32 arithmetic as the device does it): [n,4] pixel indices, tap order (y0,x0) (y0,x1) (y1,x0) (y1,x1)."""
-    u, v = uv[:, 0].astype(np.float32), uv[:, 1].astype(np.float32)
-    ix = u * np.float32(0.25) - np.float32(0.5)
-    iy = v * np.float32(0.25) - np.float32(0.5)
-    x0, y0 = np.floor(ix).astype(np.int64), np.floor(iy).astype(np.int64)
-    x1, y1 = np.clip(x0 + 1, 0, Wf - 1), np.clip(y0 + 1, 0, Hf - 1)
-    x0, y0 = np.clip(x0, 0, Wf - 1), np.clip(y0, 0, Hf - 1)
-    return np.stack([y0 * Wf + x0, y0 * Wf + x1, y1 * Wf + x0, y1 * Wf + x1], 1)
-
-
-def cam_map_statement(uv, cnt, n_max, Hf, Wf):
-    B = uv.shape[0]
-    starts, ents, base = [], [], 0
-    for b in range(B):
-        n = min(int(cnt[b]), n_max)
-        pix = taps_statement(uv[b, :n], Hf, Wf).reshape(-1)
-        key = np.arange(n * 4)
-        order = np.lexsort((key, pix))
-        c = np.bincount(pix, minlength=Hf * Wf + 1)
-        starts.append(base + np.concatenate([[0], np.cumsum(c)])[:Hf * Wf + 1])
-        ents.append(key[order])
-        base += n * 4
-    return np.concatenate(starts).astype(np.int32), np.concatenate(ents).astype(np.int32)
 
 
 def _uv_case(B, n_max, Hf, Wf, seed, crowd=False):
@@ -147,7 +109,7 @@ def test_camera_pixel_map_exact(B, n_max, Hf, Wf, crowd):
 def test_fusion_backward_det_matches_pixel_run_kernel(Cb, K, case):
     """The harness of tests/test_gpu_fusion.py::test_fusion_backward_by_point_matches_pixel_run_kernel with the deterministic kernel
     in the place of the by-point ones: dP (compute dtype, buffer starts as NaN), dW1d, db1 against dcf_fusion_gather_bwd; same
-    tolerances."""
+    tolerances.  The pixel-run kernel used as the reference here is itself pinned to the fp64 statement in tests/test_gpu_fusion_edges.py."""
     ops, H = pkg("ops"), pkg("_hip")
     h, w, stride, n_max = 24, 40, 4, 300
     xyz, cnt, idx, n, g = _knn_case(case, K, h, w, stride, n_max)
@@ -186,7 +148,7 @@ def test_fusion_backward_det_matches_pixel_run_kernel(Cb, K, case):
 def test_fusion_backward_det_at_cfg2_size(K, dtype):
     """tests/test_gpu_benchsize.py::test_fusion_backward_by_point_at_cfg2_size's harness (its cloud, its fp64 statement with the
     slack for ambiguous ReLU decisions, its tolerances) around the deterministic kernel, all four sites."""
-    from test_gpu_benchsize import _cfg2_frame, fusion_bwd_statement
+    from test_gpu_benchsize import _cfg2_frame
     ops, H = pkg("ops"), pkg("_hip")
     g, pc, uv, n = _cfg2_frame()
     n_max = pc.shape[0]
@@ -264,17 +226,11 @@ def test_point_sample_backward_det_at_cfg2_size(dtype):
     gF = torch.full((1, Hf, Wf, Cf), float("nan"), device="cuda")
     cam = ops.cam_invert(uvt.cuda().unsqueeze(0), cnt, uvt.shape[0], Hf, Wf)
     ops.point_sample_bwd_det(code, gfp.cuda().unsqueeze(0), uvt.cuda().unsqueeze(0), cam, gF)
-    u, v = uvt[:n, 0], uvt[:n, 1]
-    ix, iy = u * 0.25 - 0.5, v * 0.25 - 0.5
-    x0f, y0f = torch.floor(ix), torch.floor(iy)
-    wx, wy = (ix - x0f).double(), (iy - y0f).double()
-    x0, y0 = x0f.long(), y0f.long()
-    x1, y1 = (x0 + 1).clamp(0, Wf - 1), (y0 + 1).clamp(0, Hf - 1)
-    x0, y0 = x0.clamp(0, Wf - 1), y0.clamp(0, Hf - 1)
+    pix, wts = tap_weights(uv[:n], Hf, Wf)
     want = torch.zeros(Hf * Wf, Cf, dtype=torch.float64)
     g64 = gfp[:n].double()
-    for yy, xx, ww in ((y0, x0, (1 - wy) * (1 - wx)), (y0, x1, (1 - wy) * wx), (y1, x0, wy * (1 - wx)), (y1, x1, wy * wx)):
-        want.index_add_(0, yy * Wf + xx, g64 * ww[:, None])
+    for t in range(4):
+        want.index_add_(0, pix[:, t], g64 * wts[:, t, None])
     got = gF.cpu().double().reshape(Hf * Wf, Cf)
     print("point-sample backward (gather) at cfg2 size, %s: off by %.3g of %.3g" % (dtype, float((got - want).abs().max()), float(want.abs().max())))
     assert float((got - want).abs().max()) <= 2e-5 * float(want.abs().max())

@@ -193,7 +193,8 @@ def test_side_stream_geometry_matches_inline():
 def test_fusion_backward_by_point_matches_pixel_run_kernel(Cb, K, case):
     """dcf_fusion_invert + dcf_fusion_gather_bwd_inv (pairs sorted by point) against dcf_fusion_gather_bwd (pixel runs)
     on the same KNN map: dP, dW1d, db1.  Edge cases: one point owning every pixel (runs far longer than a wave's
-    slice), no valid point at all (every index -1)."""
+    slice), no valid point at all (every index -1).  The pixel-run kernel used as the reference here is itself pinned to the fp64
+    statement in tests/test_gpu_fusion_edges.py."""
     ops, H = pkg("ops"), pkg("_hip")
     g = torch.Generator().manual_seed(7)
     h, w, stride, n_max = 24, 40, 4, 300
