@@ -149,6 +149,8 @@ SIGNATURES = {
     "dcf_adam_step_guarded": (c_int, [P, P, P, P, c_i64, c_float, c_float, c_float, P, P]),
     # training recipe: AdamW decay + weight EMA in the Adam pass (csrc/optim.hip)
     "dcf_adamw_ema_step": (c_int, [P, P, P, P, P, P, c_i64, c_float, c_float, c_float, c_float, c_int, c_float, c_float, c_float, P, P]),
+    # gradient accumulation: dst = src / dst += src on the arena or a range of it (csrc/optim.hip)
+    "dcf_grad_accumulate": (c_int, [P, P, c_i64, c_int, P]),
 }
 
 

@@ -191,3 +191,72 @@ extern "C" int dcf_adamw_ema_step(float *params, const float *grads, float *m, f
 #undef DCF_ADAMW
     return DCF_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Gradient accumulation: dst = src (mode 0) or dst = dst + src (mode 1) over n floats, one fp32 add per
+// element, no atomics -- every element has one writer.  Called on the whole gradient arena and on sub-ranges of it (the gradient
+// buckets), so the pointers are only 4-byte aligned:
+//     vec     dst and src share their offset modulo 16 bytes: `head` (0..3) elements up to the first 16-byte boundary go element by
+//             element (lane t < head of the first workgroup takes element t), the rest is k_adamw_ema_flat's shape -- one float4 group
+//             per lane, the ragged tail element by element
+//     scalar  otherwise: one element per lane
+// Both compute dst[i] + src[i] per element, so the result does not depend on the path.
+template <int MODE>
+__device__ __forceinline__ float accum1(float d, float s) { return MODE == 0 ? s : d + s; }
+
+template <int MODE>
+__global__ void __launch_bounds__(kThreads) k_grad_accum_vec(float *dst, const float *src, int64_t n, int head)
+{
+    const int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (t < head) dst[t] = accum1<MODE>(MODE == 0 ? 0.f : dst[t], src[t]);      // head <= n: the host clamps it
+    const int64_t i4 = head + t * 4;
+    if (i4 >= n) return;
+    if (i4 + 4 <= n) {
+        const float4 s = ld4(src + i4);
+        float4 d = s;
+        if (MODE != 0) {
+            d = ld4(dst + i4);
+            d.x = d.x + s.x; d.y = d.y + s.y; d.z = d.z + s.z; d.w = d.w + s.w;
+        }
+        st4(dst + i4, d);
+    } else {
+        for (int64_t i = i4; i < n; ++i) dst[i] = accum1<MODE>(MODE == 0 ? 0.f : dst[i], src[i]);
+    }
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(kThreads) k_grad_accum_scalar(float *dst, const float *src, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (i < n) dst[i] = accum1<MODE>(MODE == 0 ? 0.f : dst[i], src[i]);
+}
+
+extern "C" int dcf_grad_accumulate(float *dst, const float *src, int64_t n, int mode, dcf_stream_t stream)
+{
+    DCF_REQUIRE(dst && src && n >= 0 && (mode == 0 || mode == 1), "dcf_grad_accumulate: bad arguments (dst %p, src %p, n %lld, mode %d)",
+                (void *)dst, (const void *)src, (long long)n, mode);
+    DCF_REQUIRE(aligned(dst, 4) && aligned(src, 4), "dcf_grad_accumulate: dst and src must be 4-byte aligned");
+    DCF_REQUIRE(n <= ((int64_t)1 << 38), "dcf_grad_accumulate: n %lld is over the launch grid's range", (long long)n);
+    DCF_REQUIRE(!overlaps(dst, src, n), "dcf_grad_accumulate: dst and src overlap");
+    if (n == 0) return DCF_OK;
+    const double bytes = (double)n * (mode == 0 ? 8.0 : 12.0);
+    hipStream_t s = S(stream);
+    if ((((uintptr_t)dst ^ (uintptr_t)src) & 15) == 0) {
+        int64_t head = (int64_t)(((16 - ((uintptr_t)dst & 15)) & 15) / 4);
+        if (head > n) head = n;
+        int64_t lanes = (n - head + 3) / 4;
+        if (lanes < head) lanes = head;
+        const int blocks = cdiv(lanes, kThreads);
+        if (mode == 0)
+            DCF_LAUNCH_B("grad_accumulate", bytes, s, hipLaunchKernelGGL((k_grad_accum_vec<0>), dim3(blocks), dim3(kThreads), 0, s, dst, src, n, (int)head));
+        else
+            DCF_LAUNCH_B("grad_accumulate", bytes, s, hipLaunchKernelGGL((k_grad_accum_vec<1>), dim3(blocks), dim3(kThreads), 0, s, dst, src, n, (int)head));
+    } else {
+        const int blocks = cdiv(n, kThreads);
+        if (mode == 0)
+            DCF_LAUNCH_B("grad_accumulate", bytes, s, hipLaunchKernelGGL((k_grad_accum_scalar<0>), dim3(blocks), dim3(kThreads), 0, s, dst, src, n));
+        else
+            DCF_LAUNCH_B("grad_accumulate", bytes, s, hipLaunchKernelGGL((k_grad_accum_scalar<1>), dim3(blocks), dim3(kThreads), 0, s, dst, src, n));
+    }
+    return DCF_OK;
+}

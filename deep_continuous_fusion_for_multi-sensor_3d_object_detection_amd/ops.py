@@ -334,6 +334,18 @@ def adamw_ema_step(params, grads, m, v, lr, beta1, beta2, eps, step, gscale=1.0,
            ema_omd, None if state is None else state.raw, H.stream_ptr())
 
 
+def grad_accumulate(dst, src, mode):
+    """dcf_grad_accumulate (csrc/optim.hip): dst = src (mode 0) or dst += src (mode 1) over two contiguous fp32 device tensors of one
+    size -- the gradient arena or a range of it; they must not overlap."""
+    if dst.dtype != torch.float32 or src.dtype != torch.float32 or dst.numel() != src.numel():
+        raise ValueError("grad_accumulate: two fp32 tensors of one size (got %s[%d], %s[%d])" % (dst.dtype, dst.numel(), src.dtype, src.numel()))
+    if not (dst.is_contiguous() and src.is_contiguous()):
+        raise ValueError("grad_accumulate: dst and src must be contiguous")
+    if dst.numel() == 0:                                   # (an empty tensor has no address to pass)
+        return
+    H.call("dcf_grad_accumulate", dst, src, dst.numel(), int(mode), H.stream_ptr())
+
+
 # ------------------------------------------------------------------ geometry
 class GridSpec(object):
     """Grid constants of CarlaDataset.__init__ (data_import_carla.py:35-43) and the filter

@@ -72,6 +72,33 @@ def parse_guard_config(cfg):
             "max_norm": clip}
 
 
+def parse_accum_config(cfg):
+    """Gradient accumulation (config_carla.yaml), validated: None = off (grad_accum_steps absent or 1: today's
+    step), else {"steps": k, "reduce": "mean" | "sum"}.
+      grad_accum_steps     k >= 1: one optimiser step per k one_step calls (micro-steps)
+      grad_accum_reduce    mean (default): the optimiser sees (g_1 + ... + g_j) / j over the window's j micro-steps; sum: the plain sum
+    Bad values raise ValueError, whether accumulation is on or not."""
+    k = cfg.get("grad_accum_steps", 1)
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError("grad_accum_steps must be an integer >= 1 (got %r)" % (k,))
+    red = cfg.get("grad_accum_reduce", "mean")
+    if not isinstance(red, str) or red.strip().lower() not in ("mean", "sum"):
+        raise ValueError("grad_accum_reduce must be mean or sum (got %r)" % (red,))
+    if k == 1:
+        return None
+    return {"steps": int(k), "reduce": red.strip().lower()}
+
+
+def window_factor(accum, j):
+    """What a window of j micro-steps multiplies into the optimiser's gradient scale: 1 / j under `mean`, 1 under `sum` (and with
+    accumulation off, accum None)."""
+    if accum is None or accum["reduce"] == "sum":
+        return 1.0
+    if isinstance(j, bool) or not isinstance(j, int) or j < 1:
+        raise ValueError("a window holds at least one micro-step (got %r)" % (j,))
+    return 1.0 / j
+
+
 AUGMENT_KEYS = ("enabled", "seed", "rotation_deg", "scale", "flip_prob", "point_drop")
 
 
@@ -268,11 +295,18 @@ def broadcast_from_rank0(t):
 
 
 class Train(nn.Module):
+    # gradient accumulation, off: no open window, and the bucket hook adds nothing (one_step sets these per call)
+    accum, accum_buf, _accum_index, _accum_closing, _accum_added = None, None, 0, False, 0
+
     def __init__(self, config):
         super(Train, self).__init__()
         self.config = config
         # deterministic: true -- one_step as a pure function of the state and the frames (per rank); bad combinations raise here
         self.deterministic = parse_deterministic_config(config)
+        # gradient accumulation (grad_accum_steps / grad_accum_reduce; None = off, the default): one optimiser step per window of k
+        # one_step calls.  The accumulator (below) is a second gradient arena at a fixed address, filled outside the captured graphs;
+        # the count of the open window's micro-steps lives on the host
+        self.accum = parse_accum_config(config)
         self.loss_total = LossTotal(config)
         self.model = ObjectDetection_DCF(config).cuda()
         self.loss_value = None
@@ -307,6 +341,10 @@ class Train(nn.Module):
         # (seed, rank, aug_calls, frame) -- no generator state, the count is all a checkpoint has to carry
         self.augment = parse_augment_config(config)
         self.aug_calls = 0
+        # the accumulator of gradient accumulation: allocated only when a window holds more than one micro-step
+        self.accum_buf = torch.empty_like(self.model.flat_grads.detach()) if self.accum is not None else None
+        self._accum_index = 0
+        self._accum_closing, self._accum_added = False, 0
 
     def sync_replicas(self):
         """Identical replicas: rank 0's parameters, buffers, optimiser moments and step count win (called at construction;
@@ -483,10 +521,14 @@ class Train(nn.Module):
             if b <= a:
                 continue
             seg = g[a:b]
+            if self._accum_closing:
+                # the window's closing micro-step: the range's earlier micro-gradients come in first (behind the finalisation launch,
+                # same stream, in front of the bf16 cast), so that the collective below carries the window's sum
+                ops.grad_accumulate(seg, self.accum_buf[a:b], 1)
+                self._accum_added += b - a
             if self.grad_bucket_dtype == "bf16":
                 # the bucket goes out in bf16: rounded here (behind the finalisation launch, same stream), summed by the collective,
                 # widened back into the fp32 arena once the collective is done (one_step, before the optimiser step)
-                from . import ops
                 from . import _hip as H
                 if self._g16 is None or self._g16.numel() != g.numel():
                     self._g16 = torch.empty(g.numel(), dtype=torch.bfloat16, device=g.device)
@@ -518,8 +560,13 @@ class Train(nn.Module):
         grouped = dist.is_available() and dist.is_initialized()
         overlap = ((n > 1 or (self.overlap_force and grouped)) and self.overlap_allreduce and not self.model.graphs_wanted(lidar_voxel.shape[0])
                    and self.model._backend is not None)
+        # gradient accumulation: micro-step j of its window; only the closing one exchanges gradients and reaches the optimiser
+        j = self._accum_index + 1
+        closing = self.accum is None or j >= self.accum["steps"]
+        overlap = overlap and closing
         premul = 1.0
         self._pending, self._reduced, self._widen = [], 0, []
+        self._accum_closing, self._accum_added = closing and j > 1, 0
         if overlap:
             self.model._backend.bucket_hook = self._bucket_ready
         try:
@@ -532,6 +579,19 @@ class Train(nn.Module):
         finally:
             if overlap:
                 self.model._backend.bucket_hook = None
+            self._accum_closing = False
+        if not closing:
+            # acc = g (the window's first micro-step) or acc += g: the left fold S_j = S_(j-1) + g_j.  No collective, no scan of
+            # the gradient, no optimiser launch; parameters, moments, clocks and the average stay where they are
+            ops.grad_accumulate(self.accum_buf, self.model.flat_grads, 0 if j == 1 else 1)
+            self._accum_index = j
+            self._release_geometry(extra)
+            return
+        if j > 1 and self._accum_added != self.model.flat_grads.numel():
+            if self._accum_added:
+                raise RuntimeError("gradient buckets added the accumulator to %d of %d elements" % (self._accum_added, self.model.flat_grads.numel()))
+            ops.grad_accumulate(self.model.flat_grads, self.accum_buf, 1)        # g += acc: the arena now holds the window's sum
+        self._accum_index = 0
         if overlap and self._reduced == self.model.flat_grads.numel():
             for w in self._pending:
                 w.wait()
@@ -547,11 +607,36 @@ class Train(nn.Module):
             if self._reduced:
                 raise RuntimeError("gradient buckets covered %d of %d elements" % (self._reduced, self.model.flat_grads.numel()))
             allreduce_grads(self.model.flat_grads)
-        self.optimizer.step(1.0 / (n * premul))
+        if self.accum is None:
+            self.optimizer.step(1.0 / (n * premul))
+        else:                                      # the window's 1 / j (mean) rides in the gradient scale, by value
+            self.optimizer.step((1.0 / (n * premul)) * window_factor(self.accum, j))
+        self._release_geometry(extra)
+
+    def _release_geometry(self, extra):
         st = (extra.get("geom") or {}).get("_set")
         if st is not None:                         # the geometry buffers of this step may be refilled from here on
             st["free_event"] = torch.cuda.Event()
             st["free_event"].record()
+
+    # ------------------------------------------------------------------ gradient accumulation
+    def accum_index(self):
+        """Micro-steps gathered in the open window (host int, no device read): 0 at a window boundary, and always with accumulation off."""
+        return self._accum_index
+
+    def finish_window(self):
+        """Close a short window: the optimiser step with the j micro-steps gathered so far (`mean` divides by j), through the same
+        exchange and optimiser calls as a full one -- the exchange is one all-reduce of the whole fp32 arena, since no backward
+        runs here to overlap with.  No-op at a boundary and with accumulation off."""
+        j = self._accum_index
+        if self.accum is None or j == 0:
+            return
+        if self._ema_swapped:
+            raise RuntimeError("finish_window inside ema_weights(): the parameter arena holds the averaged weights")
+        ops.grad_accumulate(self.model.flat_grads, self.accum_buf, 0)            # the arena held g_j alone: it now holds S_j
+        self._accum_index = 0
+        n = allreduce_grads(self.model.flat_grads)
+        self.optimizer.step((1.0 / n) * window_factor(self.accum, j))
 
     def one_step_raw(self, frame_geometry, batch):
         """One train step from a FrameLoader batch (raw points + image in HBM): geometry on the side stream, then one_step."""
@@ -661,8 +746,13 @@ class Train(nn.Module):
             opt["ema"] = self.optimizer.ema.cpu()
         if self.optimizer.amp is not None:         # the guard state (scale, growth tracker, counters), without the partials workspace
             opt["amp"] = self.optimizer.amp.header.cpu()
-        torch.save({"model": sd, "optimizer": opt, "epoch": int(epoch), "loss_calls": int(getattr(self.loss_total, "calls", 0)),
-                    "aug_calls": int(self.aug_calls)}, path)
+        ck = {"model": sd, "optimizer": opt, "epoch": int(epoch), "loss_calls": int(getattr(self.loss_total, "calls", 0)),
+              "aug_calls": int(self.aug_calls)}
+        if self.accum is not None:                 # gradient accumulation: where the window stands and, inside one, its sum so far
+            ck["accum_index"] = int(self._accum_index)
+            if self._accum_index:
+                ck["accum"] = self.accum_buf.cpu()
+        torch.save(ck, path)
 
     def load_checkpoint(self, path):
         ck = torch.load(path, map_location="cpu")
@@ -678,6 +768,15 @@ class Train(nn.Module):
         if hasattr(self.loss_total, "calls"):       # device sampling: a resumed run continues the draw sequence instead of replaying it
             self.loss_total.calls = int(ck.get("loss_calls", self.optimizer.step_count))
         self.aug_calls = int(ck.get("aug_calls", self.optimizer.step_count))    # augmentation: the draw sequence continues likewise
+        # gradient accumulation: a checkpoint without the keys (or written at a boundary) loads at a window boundary; one written
+        # inside a window needs a trainer that can hold it
+        idx = int(ck.get("accum_index", 0))
+        if idx and (self.accum is None or idx >= self.accum["steps"] or ck.get("accum") is None):
+            raise ValueError("the checkpoint was written %d micro-steps into an accumulation window: load it with grad_accum_steps > %d"
+                             % (idx, idx))
+        if idx:
+            self.accum_buf.copy_(ck["accum"])
+        self._accum_index = idx
         return int(ck.get("epoch", 0))
 
     def get_loss_value(self, lidar_voxel, camera_image, object_data, num_ref_box, **extra):
@@ -806,6 +905,10 @@ def main():
     test_loader = FrameLoader(test_dataset, config["batch_size"], shuffle=False, num_workers=int(config.get("num_workers", 4)),
                               drop_last=True) if rank0 else None
     os.makedirs("./saved_model", exist_ok=True)
+    if rank0 and training.accum is not None:
+        k = training.accum["steps"]
+        print("gradient accumulation: %d micro-steps per optimiser step (%s), effective batch %d = %d frames x %d ranks x %d"
+              % (k, training.accum["reduce"], config["batch_size"] * world() * k, config["batch_size"], world(), k))
     for epoch in range(config["num_epoch"]):
         if sampler is not None:
             sampler.set_epoch(epoch)
@@ -834,6 +937,8 @@ def main():
                     print("batch %d: validation loss %.4f, positives %d, labelled %d, TP@0.5 %d" % (batch_ndx, mean, npos, nt, tp[0.5]))
                     _print_ranked(tester)
                 _eval_barrier()
+        training.finish_window()                                           # a short last window steps with what it has: the
+        #                                                                    evaluation below and the next save see no open window
         if rank0 and terms_n:
             cls_mean, reg_mean, npos_mean = (terms_sum / terms_n).tolist()
             print("epoch %d: focal classification %.4f, regression %.4f, positive cells %.1f (batch means)" % (epoch, cls_mean, reg_mean, npos_mean))

@@ -454,6 +454,16 @@ int dcf_adamw_ema_step(float *params, const float *grads, float *m, float *v, fl
                        float lr, float beta1, float beta2, float eps, int step, float gscale, float decay_mul, float ema_omd,
                        const dcf_amp_state *state, dcf_stream_t stream);
 
+/* (version 202 still: tests/test_amp_host.py pins the number, and the entry adds to the ABI without changing any of it; probe for the
+ * symbol) Gradient accumulation (`grad_accum_steps`; csrc/optim.hip): one streaming pass over n floats,
+ *     mode 0   dst[i] = src[i]
+ *     mode 1   dst[i] = dst[i] + src[i]          one fp32 add per element, nothing contracted, no atomics
+ * on the whole gradient arena or on a sub-range of it (a gradient bucket): dst and src need only be 4-byte aligned.  When they share
+ * their offset modulo 16 bytes the pass moves one float4 per lane (a scalar head up to the first 16-byte boundary, a ragged tail
+ * element by element), otherwise one float per lane; the result does not depend on which.  n == 0 launches nothing.  NULL pointers,
+ * n < 0, another mode, or [dst, dst + n) overlapping [src, src + n) are errors: nothing is launched. */
+int dcf_grad_accumulate(float *dst, const float *src, int64_t n, int mode, dcf_stream_t stream);
+
 /* dcf_fusion_gather_bwd driven by dcf_fusion_invert's pairs (Cb in {64,128,192,256}): same sums, no idx -> point -> row
  * dependency chain.  The map's pairs are [*e_begin, *e_end) = start[g*(n_max+1)], start[g*(n_max+1)+n_max];
  * max_entries = K*h*w sizes the grid.
