@@ -117,9 +117,13 @@ __global__ void __launch_bounds__(256) k_weight_prep_f8(const dcf_conv_param *ta
     am = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3])) * fabsf(bn);
     const float sw = am > 0.f ? 448.f / am : 1.f;
     const float m = bn * sw;
-    for (int k = threadIdx.x; k < K / 4; k += 256) {
-        const float4 v = ld4(src + k * 4);
-        dst[k] = pack4_f8(v.x * m, v.y * m, v.z * m, v.w * m);
+    if (am == 0.f) {                             // all-zero row (or a zero BN scale): zero BITS, not 0 * negative = -0 (0x80)
+        for (int k = threadIdx.x; k < K / 4; k += 256) dst[k] = 0u;
+    } else {
+        for (int k = threadIdx.x; k < K / 4; k += 256) {
+            const float4 v = ld4(src + k * 4);
+            dst[k] = pack4_f8(v.x * m, v.y * m, v.z * m, v.w * m);
+        }
     }
     if (threadIdx.x == 0) wsarena[f.wscale_off + co] = am > 0.f ? am / 448.f : 1.f;
 }

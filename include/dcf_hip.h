@@ -247,7 +247,14 @@ int dcf_stem7x7_wgrad(int dtype, const void *img4, const void *gy, float *slabs,
 /* Per-step parameter preparation (table driven, one launch for the whole net):
  * for conv i: scale = gamma*rsqrt(var+eps) (or 1), shift = beta - mean*scale (or 0),
  * w_fwd = cast(scale[co]*W), w_dgrad = transpose of the same.  Descriptor table lives on
- * the device (struct dcf_conv_param, below).  cin and cout_pad must be multiples of 32. */
+ * the device (struct dcf_conv_param, below).  cin and cout_pad must be multiples of 32.
+ * What the kernels rely on without checking it (they load and store 16 bytes per lane):
+ *   - w_off is a multiple of 4 elements (and so is every row, K = taps*cin being a multiple of 32);
+ *   - wfwd_off, wdgrad_off and w8_off (dcf_f8_param) are 16-byte aligned -- the product rounds them to 256 bytes;
+ *   - slab_off is a multiple of 4 elements;
+ *   - a range a layer owns in one arena overlaps no other layer's: the kernels write rows co < cout_pad of the weight
+ *     images, scale / shift and wscale (zeros for co >= cout) and rows co < cout of the gradients, nothing else.
+ * (pinned by tests/test_gpu_prep_finalize.py against the fp64 statements of tests/_prep_ref.py) */
 typedef struct dcf_conv_param {
     int64_t w_off;      /* element offset of W [Cout][taps][Cin] fp32 in the parameter arena */
     int64_t gamma_off;  /* BN gamma/beta offsets in the parameter arena, -1 = no BN            */
@@ -266,12 +273,14 @@ int dcf_weight_prep(int dtype, const dcf_conv_param *table, int nconv, const flo
                     void *warena, float *ssarena, float eps, dcf_stream_t stream);
 /* Reduce wgrad slabs in split order and apply the folded-BN chain rule:
  * dW = scale*G, dgamma = (<W,G> - mean*dbeta)*invstd, dbeta = sum over the 4*nsplit rows of gsum[.][co]. */
-/* max_cout = the largest cout of the table (grid width). */
+/* max_cout = the largest cout of the table (grid width): a layer whose cout exceeds it keeps rows max_cout .. cout - 1
+ * of its gradients UNFINALISED (no workgroup exists for them, no error is raised). */
 int dcf_wgrad_finalize(const dcf_conv_param *table, int nconv, int max_cout, const float *params, const float *buffers,
                        const float *ssarena, const float *slabs, const float *gsum, float *grads, float eps,
                        dcf_stream_t stream);
 /* Same, with the layers' cout values on the HOST (cout_host[nconv], nconv <= 256): one workgroup per (conv, output channel)
- * exactly, instead of a max_cout x nconv grid whose surplus workgroups exit at once. */
+ * exactly, instead of a max_cout x nconv grid whose surplus workgroups exit at once.  Above 256 layers the call is
+ * still valid: it launches the grid form with max_cout = max(cout_host) -- same bits, no error. */
 int dcf_wgrad_finalize_rows(const dcf_conv_param *table, int nconv, const int32_t *cout_host, const float *params, const float *buffers,
                             const float *ssarena, const float *slabs, const float *gsum, float *grads, float eps,
                             dcf_stream_t stream);
@@ -289,7 +298,9 @@ int dcf_fp8_act_scale(float amax, float *scale);
  * (one hot address would serialise the atomics).  n multiple of 8. */
 int dcf_cast_fp8(int dtype, const void *x, void *x8, const float *amax_prev, float *amax_cur, int64_t n, dcf_stream_t stream);
 /* Per-conv fp8 weight images: w8 [cout_pad][taps][cin] = q(bn_scale*W * 448/amax_co) at byte offset w8_off of w8arena,
- * dequantisation factors amax_co/448 at element offset wscale_off of wsarena (w8_off < 0: conv not on the fp8 path).
+ * dequantisation factors amax_co/448 at element offset wscale_off of wsarena (w8_off < 0: conv not on the fp8 path:
+ * nothing of it is touched, its amax block included).  An all-zero row gets zero bits and the factor 1, rows
+ * co >= cout zero bits and the factor 0.
  * Also rolls each conv's activation maxima: amax holds DCF_F8_AMAX_STRIDE floats per conv, [0..63] the partial maxima of
  * the current step and [64] the previous step's maximum (the scale source): prev <- max(cur[0..63]), cur <- 0. */
 #define DCF_F8_AMAX_STRIDE 80
