@@ -164,7 +164,10 @@ int dcf_image_to_nhwc4(int dtype, const uint8_t *img, void *y, int B, int H, int
  * Replaces nn.Conv2d (+ folded eval BatchNorm + residual + ReLU) of model.py:15-41,147-157.
  * Implicit GEMM on MFMA; x [B,H,W,Cin], w [Cout][kh][kw][Cin] (dtype), y [B,Ho,Wo,Cout].
  * y = act(conv(x,w) + shift[c] + res);  shift fp32 [Cout] or NULL; res (dtype, like y) or NULL.
- * Cin*esize must be a multiple of 64 bytes; Cout a multiple of 32. */
+ * Cin*esize must be a multiple of 64 bytes; Cout a multiple of 32.
+ * Every tensor of the convolution entries below (activations, weights, shift, residuals, masks, slabs, gsum) must be 16-byte
+ * aligned -- the kernels move 16 bytes per access -- and needs no more than that (tests/test_gpu_conv_exact.py writes every
+ * output 16 bytes past a 32-byte boundary). */
 int dcf_conv2d_fwd(int dtype, const void *x, const void *w, const float *shift, const void *res, void *y,
                    int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad,
                    int relu, dcf_stream_t stream);
