@@ -54,6 +54,8 @@ SIGNATURES = {
     "dcf_conv2d_fwd_rowscale": (c_int, [c_int, P, P, P, P, P, P] + [c_int] * 12 + [P]),
     "dcf_conv2d_dgrad": (c_int, [c_int, P, P, P, P, P] + [c_int] * 11 + [P]),
     "dcf_conv2d_dgrad_halfres": (c_int, [c_int, P, P, P, P, P, P] + [c_int] * 11 + [P]),
+    "dcf_conv2d_fwd_group": (c_int, [P, c_int, P]),
+    "dcf_conv2d_dgrad_group": (c_int, [P, c_int, P]),
     "dcf_conv3x3_chain_supported": (c_int, [c_int] * 6),
     "dcf_conv3x3_chain_workspace_bytes": (c_size_t, [c_int] * 6),
     "dcf_conv3x3_chain": (c_int, [c_int, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P]),
@@ -176,6 +178,22 @@ class WgradItem(ctypes.Structure):
                 ("gsum", c_void_p), ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("Cin", ctypes.c_int32),
                 ("Cout", ctypes.c_int32), ("kh", ctypes.c_int32), ("kw", ctypes.c_int32), ("stride", ctypes.c_int32), ("pad", ctypes.c_int32),
                 ("pad_", ctypes.c_int32)]
+
+
+class ConvFwdItem(ctypes.Structure):
+    """struct dcf_conv_fwd_item of include/dcf_hip.h."""
+    _fields_ = [("dtype", ctypes.c_int32), ("relu", ctypes.c_int32), ("x", c_void_p), ("w", c_void_p), ("shift", c_void_p), ("res", c_void_p),
+                ("y", c_void_p), ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("Cin", ctypes.c_int32),
+                ("Ho", ctypes.c_int32), ("Wo", ctypes.c_int32), ("Cout", ctypes.c_int32), ("kh", ctypes.c_int32), ("kw", ctypes.c_int32),
+                ("stride", ctypes.c_int32), ("pad", ctypes.c_int32), ("pad_", ctypes.c_int32)]
+
+
+class ConvDgradItem(ctypes.Structure):
+    """struct dcf_conv_dgrad_item of include/dcf_hip.h."""
+    _fields_ = [("dtype", ctypes.c_int32), ("pad_", ctypes.c_int32), ("gy", c_void_p), ("wt", c_void_p), ("res", c_void_p), ("mask", c_void_p),
+                ("gx", c_void_p), ("B", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("Cin", ctypes.c_int32),
+                ("Ho", ctypes.c_int32), ("Wo", ctypes.c_int32), ("Cout", ctypes.c_int32), ("kh", ctypes.c_int32), ("kw", ctypes.c_int32),
+                ("stride", ctypes.c_int32), ("pad", ctypes.c_int32), ("pad2_", ctypes.c_int32)]
 
 
 CHAIN_MAX_LAYERS = 24        # DCF_CHAIN_MAX_LAYERS

@@ -35,6 +35,8 @@ class HipBackend(object):
         self._chain_ok, self._chain_ws, self._chain_tab = {}, {}, {}     # chain launches: support per shape, arrival counters per shape, ctypes tables per length
         self._fn_fwd, self._fn_dgrad = H.fn("dcf_conv2d_fwd"), H.fn("dcf_conv2d_dgrad")
         self._fn_bnf, self._fn_bnb = H.fn("dcf_bn_train_fwd"), H.fn("dcf_bn_train_bwd")
+        self._fn_fwdg, self._fn_dgradg = H.fn("dcf_conv2d_fwd_group"), H.fn("dcf_conv2d_dgrad_group")
+        self._gfw, self._gdg = {}, {}      # grouped forward convolutions / input gradients: ctypes item arrays per layer sequence
         self._bbase = buffers.data_ptr()
         self._pbase, self._gbase = params.data_ptr(), grads.data_ptr()     # (arena slices go to the C ABI as raw addresses: a view costs ~2.5 us)
         self.bn_train = False          # batch statistics instead of running statistics (train-mode BatchNorm)
@@ -401,6 +403,75 @@ class HipBackend(object):
         if rc:
             H.fail("dcf_conv2d_dgrad", rc)
         return gx
+
+    # ------------------------------------------------------------------ grouped launches of independent layers
+    def conv_fwd_group(self, specs):
+        """specs: (layer, x, res, relu[, nxt]) of forward convolutions that do NOT depend on each other.  Returns their outputs in
+        order -- the values of conv_fwd layer by layer; layers that the generic kernel runs with the same instantiation share one
+        launch (dcf_conv2d_fwd_group).  Train-mode BatchNorm, fp32 and a member on the fp8 path take the per-layer calls."""
+        n = len(specs)
+        if (n < 2 or self.bn_train or self.dtype == H.F32
+                or (self.has_fp8 and any(self._use_fp8(s[0], s[1].shape[:3]) for s in specs))):
+            return [self.conv_fwd(*s) for s in specs]
+        # the item array of a call site is the previous step's with new addresses: kept per (layer, input shape) sequence
+        key = tuple([(s[0].idx, s[1].shape) for s in specs])
+        ent = self._gfw.get(key)
+        if ent is None:
+            items, oshp = (H.ConvFwdItem * n)(), []
+            for i, s in enumerate(specs):
+                L = s[0]
+                B, Hh, W, Cin = s[1].shape
+                Ho, Wo = ops.conv_out_size(Hh, L.kh, L.stride, L.pad), ops.conv_out_size(W, L.kw, L.stride, L.pad)
+                items[i] = H.ConvFwdItem(self.dtype, 0, 0, self._wbase + L.wfwd_off, self._shift(L), 0, 0, B, Hh, W, Cin, Ho, Wo, L.cout_pad,
+                                         L.kh, L.kw, L.stride, L.pad, 0)
+                oshp.append((B, Ho, Wo, L.cout_pad))
+            if len(self._gfw) > 64:
+                self._gfw.clear()
+            ent = self._gfw[key] = (items, oshp, ctypes.addressof(items))
+        items, oshp, addr = ent
+        outs = []
+        for i, s in enumerate(specs):
+            x, res = s[1], s[2]
+            y = torch.empty(oshp[i], dtype=x.dtype, device=x.device)
+            it = items[i]
+            it.x, it.res, it.y, it.relu = x.data_ptr(), (None if res is None else res.data_ptr()), y.data_ptr(), (1 if s[3] else 0)
+            s[0].out_shape = oshp[i][:3]
+            outs.append(y)
+        rc = self._fn_fwdg(addr, n, H.stream_ptr())
+        if rc:
+            H.fail("dcf_conv2d_fwd_group", rc)
+        return outs
+
+    def conv_dgrad_group(self, specs):
+        """specs: (layer, gy, in_shape, res, mask) of input gradients that do NOT depend on each other; the values of conv_dgrad
+        layer by layer, grouped as in conv_fwd_group (dcf_conv2d_dgrad_group)."""
+        n = len(specs)
+        if n < 2 or self.bn_train or self.dtype == H.F32:
+            return [self.conv_dgrad(*s) for s in specs]
+        key = tuple([(s[0].idx, s[1].shape, s[2]) for s in specs])
+        ent = self._gdg.get(key)
+        if ent is None:
+            items = (H.ConvDgradItem * n)()
+            for i, (L, gy, ish, _, _) in enumerate(specs):
+                if L.wdgrad_off < 0:
+                    raise H.DcfError("layer %s was planned without an input gradient" % L.name)
+                gs = gy.shape
+                items[i] = H.ConvDgradItem(self.dtype, 0, 0, self._wbase + L.wdgrad_off, 0, 0, 0, ish[0], ish[1], ish[2], ish[3], gs[1], gs[2], gs[3],
+                                           L.kh, L.kw, L.stride, L.pad, 0)
+            if len(self._gdg) > 64:
+                self._gdg.clear()
+            ent = self._gdg[key] = (items, ctypes.addressof(items))
+        items, addr = ent
+        outs = []
+        for i, (L, gy, ish, res, mask) in enumerate(specs):
+            gx = torch.empty(ish, dtype=gy.dtype, device=gy.device)
+            it = items[i]
+            it.gy, it.res, it.mask, it.gx = gy.data_ptr(), (None if res is None else res.data_ptr()), (None if mask is None else mask.data_ptr()), gx.data_ptr()
+            outs.append(gx)
+        rc = self._fn_dgradg(addr, n, H.stream_ptr())
+        if rc:
+            H.fail("dcf_conv2d_dgrad_group", rc)
+        return outs
 
     # ------------------------------------------------------------------ chains (one launch per residual stage)
     # OFF unless asked for (config `conv_chain: true`, or DCF_CHAIN=1 / force in the environment).  A chain launch needs ALL its

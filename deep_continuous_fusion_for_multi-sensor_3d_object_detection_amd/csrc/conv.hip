@@ -71,8 +71,10 @@ __device__ unsigned long long g_dcf_dbg_w[4];
 // channels x TM*32 pixels.  K is walked tap by tap in chunks of KB bytes of channels.
 // LDS rows are padded by 16 B: the ds_read_b128 fragment reads are then conflict free.
 // ------------------------------------------------------------------------------------
+// The body takes the workgroup's index inside ITS layer's grid (`bid`): the single-layer kernel passes blockIdx.x, the grouped
+// kernel (k_conv_igemm_grp) blockIdx.x minus the layer's first workgroup.
 template <typename T, int KB, int TN, int TM, int WN, int WM, bool TRANSPOSED, bool DB>
-__global__ void __launch_bounds__(256) k_conv_igemm(ConvArgs a)
+__device__ __forceinline__ void igemm_body(const ConvArgs &a, const int bid)
 {
     constexpr int ES = DT<T>::size;
     constexpr int BN = WN * TN * 32, BM = WM * TM * 32;
@@ -99,7 +101,7 @@ __global__ void __launch_bounds__(256) k_conv_igemm(ConvArgs a)
     const int mtiles = PAR ? a.cls_tile[4] : cdiv_dev(a.M, BM);
     const int nblk = mtiles * nt;
     const int chunk = (nblk + 7) >> 3;
-    const int gidx = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+    const int gidx = (bid & 7) * chunk + (bid >> 3);
     if (gidx >= nblk) return;
     const int n0 = (gidx % nt) * BN;
     const int mt = gidx / nt;
@@ -305,6 +307,12 @@ __global__ void __launch_bounds__(256) k_conv_igemm(ConvArgs a)
     DCF_WEND();
 }
 
+template <typename T, int KB, int TN, int TM, int WN, int WM, bool TRANSPOSED, bool DB>
+__global__ void __launch_bounds__(256) k_conv_igemm(ConvArgs a)
+{
+    igemm_body<T, KB, TN, TM, WN, WM, TRANSPOSED, DB>(a, blockIdx.x);
+}
+
 // ------------------------------------------------------------------------------------
 // forward / dgrad kernel with LDS-DMA staging (bf16, K chunks of 128 B).  Same tiling, tap walk, XCD-aware tile order,
 // parity classes and epilogue as k_conv_igemm; what changes is how a K chunk reaches LDS: `buffer_load ... lds` pieces
@@ -316,7 +324,7 @@ __global__ void __launch_bounds__(256) k_conv_igemm(ConvArgs a)
 // keeps the 16 rows of a ds_read_b128 lane group on distinct banks; the swizzle is applied to the source chunk and to the reads.
 // ------------------------------------------------------------------------------------
 template <typename T, int KB, int TN, int TM, int WN, int WM, bool TRANSPOSED, int NS>
-__global__ void __launch_bounds__(256) k_conv_igemm_dma(ConvArgs a)
+__device__ __forceinline__ void igemm_dma_body(const ConvArgs &a, const int bid)
 {
     static_assert(DT<T>::size == 2, "16-bit element types only");
     static_assert(KB == 128 || KB == 64, "K chunks of 128 or 64 bytes");
@@ -344,7 +352,7 @@ __global__ void __launch_bounds__(256) k_conv_igemm_dma(ConvArgs a)
     const int mtiles = PAR ? a.cls_tile[4] : cdiv_dev(a.M, BM);
     const int nblk = mtiles * nt;
     const int chunk = (nblk + 7) >> 3;
-    const int gidx = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+    const int gidx = (bid & 7) * chunk + (bid >> 3);
     if (gidx >= nblk) return;
     const int n0 = (gidx % nt) * BN;
     const int mt = gidx / nt;
@@ -515,6 +523,61 @@ __global__ void __launch_bounds__(256) k_conv_igemm_dma(ConvArgs a)
     DCF_WEND();
 }
 
+template <typename T, int KB, int TN, int TM, int WN, int WM, bool TRANSPOSED, int NS>
+__global__ void __launch_bounds__(256) k_conv_igemm_dma(ConvArgs a)
+{
+    igemm_dma_body<T, KB, TN, TM, WN, WM, TRANSPOSED, NS>(a, blockIdx.x);
+}
+
+// Independent layers of ONE instantiation in one launch (dcf_conv2d_fwd_group / dcf_conv2d_dgrad_group): the arguments of up to
+// DCF_IG_GROUP layers travel in the kernel-argument segment with the first workgroup of each; a workgroup finds its layer and runs
+// the unchanged body on its index inside that layer.  Every layer's share of the grid is a multiple of 8 workgroups, so the body's
+// XCD mapping (index mod 8) sees the geometry of a launch of its own; the surplus workgroups leave at `gidx >= nblk`, before any
+// barrier.  The next layer's workgroups start while the previous layer's last ones drain: no kernel boundary, one ramp.
+#define DCF_IG_GROUP 4
+struct IgGroup {
+    ConvArgs a[DCF_IG_GROUP];
+    int off[DCF_IG_GROUP + 1];     // first workgroup of each layer
+    int n;
+};
+
+template <typename T, int KB, int TN, int TM, int WN, int WM, bool TRANSPOSED, bool DB>
+__global__ void __launch_bounds__(256) k_conv_igemm_grp(IgGroup g)
+{
+    int i = 0;
+#pragma unroll
+    for (int k = 1; k < DCF_IG_GROUP; ++k) i += (k < g.n && (int)blockIdx.x >= g.off[k]);
+    igemm_body<T, KB, TN, TM, WN, WM, TRANSPOSED, DB>(g.a[i], (int)blockIdx.x - g.off[i]);
+}
+
+template <typename T, int KB, int TN, int TM, int WN, int WM, bool TRANSPOSED, int NS>
+__global__ void __launch_bounds__(256) k_conv_igemm_dma_grp(IgGroup g)
+{
+    int i = 0;
+#pragma unroll
+    for (int k = 1; k < DCF_IG_GROUP; ++k) i += (k < g.n && (int)blockIdx.x >= g.off[k]);
+    igemm_dma_body<T, KB, TN, TM, WN, WM, TRANSPOSED, NS>(g.a[i], (int)blockIdx.x - g.off[i]);
+}
+
+// tile choice of a layer (shared by the single and the grouped launches): the biggest tile that still gives the chip >= ~1
+// workgroup per CU.  0..4 = 128x128, 64x128, 64x64, 32x128, 128x64 channels x pixels (DCF_TILE=0..4 forces one for experiments).
+static int igemm_tile(const ConvArgs &a)
+{
+    static DcfOpt force_env_o("TILE"); const char *force_env = force_env_o.str();
+    const int force = force_env ? atoi(force_env) : -1;
+    if (force == 0 && a.Cn % 128 == 0) return 0;
+    if (force == 1 && a.Cn % 64 == 0) return 1;
+    if (force == 2 && a.Cn % 64 == 0) return 2;
+    if (force == 3) return 3;
+    if (force == 4 && a.Cn % 128 == 0) return 4;
+    const int64_t want_blocks = 256;
+    auto blocks = [&](int bn, int bm) { return (int64_t)cdiv(a.M, bm) * (a.Cn / bn); };
+    if (a.Cn % 128 == 0 && blocks(128, 128) >= want_blocks) return 0;
+    if (a.Cn % 64 == 0 && blocks(64, 128) >= want_blocks) return 1;
+    if (a.Cn % 64 == 0) return 2;          // small M: 64x64 tiles give the most workgroups
+    return 3;
+}
+
 template <typename T, bool TR>
 int launch_igemm(const ConvArgs &a_in, hipStream_t s, const char *base, double flops)
 {
@@ -577,27 +640,124 @@ int launch_igemm(const ConvArgs &a_in, hipStream_t s, const char *base, double f
         }                                                                                                           \
         return DCF_OK;                                                                                              \
     } while (0)
-    // tile choice: the biggest tile that still gives the chip >= ~1 workgroup per CU
-    // (DCF_TILE=0..3 forces a tile for experiments: 128x128, 64x128, 64x64, 32x128 channels x pixels)
-    static DcfOpt force_env_o("TILE"); const char *force_env = force_env_o.str();
-    const int force = force_env ? atoi(force_env) : -1;
-    if (force == 0 && a.Cn % 128 == 0) { if (kb128) DCF_IGEMM(128, 2, 2, 2, 2); else DCF_IGEMM(64, 2, 2, 2, 2); }
-    if (force == 1 && a.Cn % 64 == 0) { if (kb128) DCF_IGEMM(128, 2, 1, 1, 4); else DCF_IGEMM(64, 2, 1, 1, 4); }
-    if (force == 2 && a.Cn % 64 == 0) { if (kb128) DCF_IGEMM(128, 1, 1, 2, 2); else DCF_IGEMM(64, 1, 1, 2, 2); }
-    if (force == 3) { if (kb128) DCF_IGEMM(128, 1, 1, 1, 4); else DCF_IGEMM(64, 1, 1, 1, 4); }
-    if (force == 4 && a.Cn % 128 == 0) { if (kb128) DCF_IGEMM(128, 2, 1, 2, 2); else DCF_IGEMM(64, 2, 1, 2, 2); }      // 128 ch x 64 px
-    const int64_t want_blocks = 256;
-    auto blocks = [&](int bn, int bm) { return (int64_t)cdiv(a.M, bm) * (a.Cn / bn); };
-    if (a.Cn % 128 == 0 && blocks(128, 128) >= want_blocks) {
-        if (kb128) DCF_IGEMM(128, 2, 2, 2, 2); else DCF_IGEMM(64, 2, 2, 2, 2);
-    } else if (a.Cn % 64 == 0 && blocks(64, 128) >= want_blocks) {
-        if (kb128) DCF_IGEMM(128, 2, 1, 1, 4); else DCF_IGEMM(64, 2, 1, 1, 4);
-    } else if (a.Cn % 64 == 0) {          // small M: 64x64 tiles give the most workgroups
-        if (kb128) DCF_IGEMM(128, 1, 1, 2, 2); else DCF_IGEMM(64, 1, 1, 2, 2);
-    } else {
-        if (kb128) DCF_IGEMM(128, 1, 1, 1, 4); else DCF_IGEMM(64, 1, 1, 1, 4);
-    }
+    const int tile = igemm_tile(a);
+    if (tile == 0) { if (kb128) DCF_IGEMM(128, 2, 2, 2, 2); else DCF_IGEMM(64, 2, 2, 2, 2); }
+    if (tile == 1) { if (kb128) DCF_IGEMM(128, 2, 1, 1, 4); else DCF_IGEMM(64, 2, 1, 1, 4); }
+    if (tile == 2) { if (kb128) DCF_IGEMM(128, 1, 1, 2, 2); else DCF_IGEMM(64, 1, 1, 2, 2); }
+    if (tile == 4) { if (kb128) DCF_IGEMM(128, 2, 1, 2, 2); else DCF_IGEMM(64, 2, 1, 2, 2); }
+    if (kb128) DCF_IGEMM(128, 1, 1, 1, 4); else DCF_IGEMM(64, 1, 1, 1, 4);
 #undef DCF_IGEMM
+}
+
+// ------------------------------------------------------------------------------------
+// Grouped launches: independent layers that the per-layer rule above sends to the SAME instantiation run in one grid.
+// Only the instantiations that the network's groups select exist (stage heads, FPN laterals, fusion GEMMs at the benchmark
+// sizes); igemm_group_launch answers DCF_EUNSUPPORTED for every other one and the caller launches those layers one by one.
+// ------------------------------------------------------------------------------------
+static const int kIgTile[5][4] = {{2, 2, 2, 2}, {2, 1, 1, 4}, {1, 1, 2, 2}, {1, 1, 1, 4}, {2, 1, 2, 2}};     // TN, TM, WN, WM of igemm_tile()'s answers
+
+static bool igemm_group_on()
+{
+    static DcfOpt o("IGEMM_GROUP"); const char *e = o.str();
+    return !(e && atoi(e) == 0);
+}
+
+// workgroups of layer a under tile `tile` (no parity classes: grouped layers never have them)
+static int64_t igemm_blocks(const ConvArgs &a, int tile)
+{
+    const int bn = kIgTile[tile][0] * kIgTile[tile][2] * 32, bm = kIgTile[tile][1] * kIgTile[tile][3] * 32;
+    return (int64_t)cdiv(a.M, bm) * (a.Cn / bn);
+}
+
+// members [0, n) of one (dtype, K chunk, tile) bucket, n in 2..DCF_IG_GROUP, in one launch
+template <typename T, bool TR>
+static int igemm_group_launch(const ConvArgs *members, int n, int kb, int tile, const char *base, hipStream_t s)
+{
+    IgGroup g;
+    int blocks = 0;
+    int64_t total = 0;
+    double flops = 0.0, bytes = 0.0;
+    for (int i = 0; i < n; ++i) {
+        const ConvArgs &a = members[i];
+        g.a[i] = a;
+        g.a[i].dbg = 0;
+        g.off[i] = blocks;
+        const int64_t nb = igemm_blocks(a, tile);
+        total += nb;
+        DCF_REQUIRE(blocks + (nb + 7) / 8 * 8 < (1ll << 30), "grouped convolution: grid too large");
+        blocks += (int)((nb + 7) / 8 * 8);
+        flops += 2.0 * a.M * a.Cn * (double)a.Ck * a.kh * a.kw;
+        bytes += (double)a.xbytes + (double)a.wbytes + (double)a.M * a.Cn * DT<T>::size * (1 + (a.res ? 1 : 0) + (a.mask ? 1 : 0));
+    }
+    for (int k = n; k <= DCF_IG_GROUP; ++k) g.off[k] = blocks;
+    for (int k = n; k < DCF_IG_GROUP; ++k) g.a[k] = g.a[0];
+    g.n = n;
+    const bool db = total <= 512;               // the single launch's rule, on the launch's total
+    static DcfOpt dma_env_o("IGEMM_DMA"); const char *dma_env = dma_env_o.str();
+    const int dma_mode = dma_env ? atoi(dma_env) : 1;
+    const bool dma = kb == 128 && dma_mode && (dma_mode == 2 || db);
+    if (kb == 128 && !dma && dma_mode == 3) return DCF_EUNSUPPORTED;      // (the 2-deep ring has no grouped form)
+    char name[64];
+#define DCF_IG_REG(KB_, TN_, TM_, WN_, WM_, DB_)                                                                                     \
+    do {                                                                                                                             \
+        snprintf(name, sizeof(name), "%s<%d,%d,%d,%d,%d%s>", base, KB_, TN_, TM_, WN_, WM_, DB_ ? ",db" : "");                       \
+        DCF_LAUNCH_WB(name, flops, bytes, s, hipLaunchKernelGGL((k_conv_igemm_grp<T, KB_, TN_, TM_, WN_, WM_, TR, DB_>), dim3(blocks), dim3(256), 0, s, g)); \
+        return DCF_OK;                                                                                                               \
+    } while (0)
+#define DCF_IG_DMA(TN_, TM_, WN_, WM_, NS_)                                                                                          \
+    do {                                                                                                                             \
+        snprintf(name, sizeof(name), "%s<128,%d,%d,%d,%d,dma%d>", base, TN_, TM_, WN_, WM_, NS_);                                    \
+        DCF_LAUNCH_WB(name, flops, bytes, s, hipLaunchKernelGGL((k_conv_igemm_dma_grp<T, 128, TN_, TM_, WN_, WM_, TR, NS_>), dim3(blocks), dim3(256), 0, s, g)); \
+        return DCF_OK;                                                                                                               \
+    } while (0)
+    if (kb == 128 && tile == 2) {                                  // 64 x 64: small-M heads, laterals, fusion GEMMs (both directions)
+        if (dma) DCF_IG_DMA(1, 1, 2, 2, 4);
+        if (db) { if constexpr (!TR) DCF_IG_REG(128, 1, 1, 2, 2, true); else return DCF_EUNSUPPORTED; }
+        DCF_IG_REG(128, 1, 1, 2, 2, false);
+    }
+    if constexpr (!TR) {
+        if (kb == 128 && tile == 1 && !dma && !db) DCF_IG_REG(128, 2, 1, 1, 4, false);     // 64 x 128: the 192-channel heads, laterals, fusion GEMMs
+        if (kb == 128 && tile == 0 && !dma && !db) DCF_IG_REG(128, 2, 2, 2, 2, false);     // 128 x 128: the large stage heads, fusion GEMMs
+        if (kb == 64 && tile == 1 && !db) DCF_IG_REG(64, 2, 1, 1, 4, false);              // 32-channel input, large M
+        if (kb == 64 && tile == 2 && db) DCF_IG_REG(64, 1, 1, 2, 2, true);                // 32-channel input, small M
+    }
+#undef DCF_IG_REG
+#undef DCF_IG_DMA
+    return DCF_EUNSUPPORTED;
+}
+
+// One group call: `args` are the layers the generic kernel takes (key[i] >= 0: (dtype, K chunk, tile) packed; < 0: not groupable).
+// Buckets of two or more go out DCF_IG_GROUP at a time; whatever is left calls single(i).
+template <bool TR, typename Single>
+static int igemm_group_issue(const std::vector<ConvArgs> &args, const std::vector<int> &key, const char *const base[3], hipStream_t s, Single single)
+{
+    const int n = (int)args.size();
+    std::vector<char> done(n, 0);
+    for (int i = 0; i < n; ++i) {
+        if (done[i]) continue;
+        std::vector<int> mem;
+        if (key[i] >= 0)
+            for (int j = i; j < n; ++j)
+                if (!done[j] && key[j] == key[i]) mem.push_back(j);
+        for (size_t p = 0; p + 1 < mem.size(); p += DCF_IG_GROUP) {
+            const int cnt = (int)std::min<size_t>(DCF_IG_GROUP, mem.size() - p);
+            if (cnt < 2) break;
+            ConvArgs m[DCF_IG_GROUP];
+            for (int k = 0; k < cnt; ++k) m[k] = args[mem[p + k]];
+            const int dt = key[i] >> 8, kb = (key[i] & 0x80) ? 128 : 64, tile = key[i] & 7;
+            const int rc = dt == DCF_F16 ? igemm_group_launch<f16_t, TR>(m, cnt, kb, tile, base[DCF_F16], s)
+                                         : igemm_group_launch<bf16_t, TR>(m, cnt, kb, tile, base[DCF_BF16], s);
+            if (rc == DCF_EUNSUPPORTED) break;          // no grouped form of this instantiation: one by one below
+            if (rc) return rc;
+            for (int k = 0; k < cnt; ++k) done[mem[p + k]] = 1;
+        }
+        if (!done[i]) {
+            const int rc = single(i);
+            if (rc) return rc;
+            done[i] = 1;
+        }
+    }
+    return DCF_OK;
 }
 
 // ------------------------------------------------------------------------------------
@@ -1533,16 +1693,15 @@ extern "C" int dcf_conv2d_fwd_rowscale(int dtype, const void *x, const void *w, 
     return conv2d_fwd_impl(dtype, x, w, shift, rowscale, res, y, B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, relu, stream);
 }
 
-static int conv2d_fwd_impl(int dtype, const void *x, const void *w, const float *shift, const float *rowscale, const void *res, void *y,
-                           int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad,
-                           int relu, dcf_stream_t stream)
+// argument checks and the kernel's view of a forward convolution (shared by the single and the grouped entry points)
+static int conv2d_fwd_args(ConvArgs &a, int dtype, const void *x, const void *w, const float *shift, const float *rowscale, const void *res,
+                           void *y, int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad, int relu)
 {
     int rc = check_conv("dcf_conv2d_fwd", dtype, Cin, Cout, kh, kw, stride);
     if (rc) return rc;
     DCF_REQUIRE(x && w && y, "dcf_conv2d_fwd: null pointer");
     DCF_REQUIRE(Ho == (H + 2 * pad - kh) / stride + 1 && Wo == (W + 2 * pad - kw) / stride + 1, "dcf_conv2d_fwd: output size mismatch");
     DCF_REQUIRE((int64_t)B * H * W * Cin < (1ll << 31) * 1, "dcf_conv2d_fwd: tensor too large for 32-bit pixel index");
-    ConvArgs a;
     a.x = (const char *)x; a.w = (const char *)w; a.shift = shift; a.res = (const char *)res; a.y = (char *)y;
     a.mask = nullptr; a.parity = 0; a.rowscale = rowscale;
     a.B = B; a.Hi = H; a.Wi = W; a.Ck = Cin; a.Ho = Ho; a.Wo = Wo; a.Cn = Cout;
@@ -1551,6 +1710,16 @@ static int conv2d_fwd_impl(int dtype, const void *x, const void *w, const float 
     DCF_REQUIRE((int64_t)B * H * W * a.pixbytes < 0xFFFFFF00ll, "dcf_conv2d_fwd: tensor exceeds the 4 GiB buffer-descriptor range");
     a.xbytes = (unsigned)((int64_t)B * H * W * a.pixbytes);
     a.wbytes = (unsigned)((int64_t)Cout * kh * kw * a.pixbytes);
+    return DCF_OK;
+}
+
+static int conv2d_fwd_impl(int dtype, const void *x, const void *w, const float *shift, const float *rowscale, const void *res, void *y,
+                           int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad,
+                           int relu, dcf_stream_t stream)
+{
+    ConvArgs a;
+    int rc = conv2d_fwd_args(a, dtype, x, w, shift, rowscale, res, y, B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, relu);
+    if (rc) return rc;
     const double flops = 2.0 * a.M * Cout * (double)Cin * kh * kw;
     if (use_rs(dtype, kh, kw, stride, pad)) {
         rc = dcf_conv3x3_sp_launch(dtype, x, w, shift, res, nullptr, y, B, H, W, Cin, Cout, relu, 0, dtype == DCF_F16 ? "conv_fwd_f16" : "conv_fwd_bf16", flops, S(stream));
@@ -1567,15 +1736,14 @@ static int conv2d_fwd_impl(int dtype, const void *x, const void *w, const float 
     return launch_igemm<bf16_t, false>(a, S(stream), "conv_fwd_bf16", flops);
 }
 
-static int conv2d_dgrad_impl(int dtype, const void *gy, const void *wt, const void *res, const void *resq, const void *mask, void *gx,
-                             int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad,
-                             dcf_stream_t stream)
+// argument checks and the kernel's view of an input gradient (shared by the single and the grouped entry points)
+static int conv2d_dgrad_args(ConvArgs &a, int dtype, const void *gy, const void *wt, const void *res, const void *resq, const void *mask,
+                             void *gx, int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad)
 {
     // roles swap: reduction channels = Cout, produced channels = Cin
     int rc = check_conv("dcf_conv2d_dgrad", dtype, Cout, Cin, kh, kw, stride);
     if (rc) return rc;
     DCF_REQUIRE(gy && wt && gx, "dcf_conv2d_dgrad: null pointer");
-    ConvArgs a;
     a.x = (const char *)gy; a.w = (const char *)wt; a.shift = nullptr; a.res = (const char *)res; a.y = (char *)gx;
     a.mask = (const char *)mask; a.resq = (const char *)resq;
     static DcfOpt par_env_o("DGRAD_PARITY"); const char *par_env = par_env_o.str();     // experiments: 0 = off, 1 = all stride-2 layers, 2 = full-line pixels only
@@ -1593,6 +1761,16 @@ static int conv2d_dgrad_impl(int dtype, const void *gy, const void *wt, const vo
     DCF_REQUIRE((int64_t)B * Ho * Wo * a.pixbytes < 0xFFFFFF00ll, "dcf_conv2d_dgrad: tensor exceeds the 4 GiB buffer-descriptor range");
     a.xbytes = (unsigned)((int64_t)B * Ho * Wo * a.pixbytes);
     a.wbytes = (unsigned)((int64_t)Cin * kh * kw * a.pixbytes);
+    return DCF_OK;
+}
+
+static int conv2d_dgrad_impl(int dtype, const void *gy, const void *wt, const void *res, const void *resq, const void *mask, void *gx,
+                             int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int kh, int kw, int stride, int pad,
+                             dcf_stream_t stream)
+{
+    ConvArgs a;
+    int rc = conv2d_dgrad_args(a, dtype, gy, wt, res, resq, mask, gx, B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad);
+    if (rc) return rc;
     const double flops = 2.0 * B * Ho * Wo * Cout * (double)Cin * kh * kw;   // algorithmic (= the forward conv's)
     if (use_rs(dtype, kh, kw, stride, pad)) {
         rc = dcf_conv3x3_sp_launch(dtype, gy, wt, nullptr, res, mask, gx, B, H, W, Cout, Cin, 0, 1, dtype == DCF_F16 ? "conv_dgrad_f16" : "conv_dgrad_bf16", flops, S(stream));
@@ -1626,6 +1804,59 @@ extern "C" int dcf_conv2d_dgrad_halfres(int dtype, const void *gy, const void *w
 {
     DCF_REQUIRE(resq, "dcf_conv2d_dgrad_halfres: null resq");
     return conv2d_dgrad_impl(dtype, gy, wt, res, resq, mask, gx, B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, stream);
+}
+
+// ---- grouped forward convolutions / input gradients of the generic implicit-GEMM kernels
+// bucket key of a layer the generic kernel takes: (dtype, 128- or 64-byte K chunks, tile)
+static int igemm_group_key(int dtype, const ConvArgs &a)
+{
+    const bool kb128 = (a.Ck * 2) % 128 == 0;
+    return (dtype << 8) | (kb128 ? 0x80 : 0) | igemm_tile(a);
+}
+
+extern "C" int dcf_conv2d_fwd_group(const dcf_conv_fwd_item *items, int n, dcf_stream_t stream)
+{
+    DCF_REQUIRE(items && n >= 0, "dcf_conv2d_fwd_group: bad arguments");
+    std::vector<ConvArgs> args(n);
+    std::vector<int> key(n, -1);
+    const bool on = igemm_group_on();
+    for (int i = 0; i < n; ++i) {
+        const dcf_conv_fwd_item &it = items[i];
+        int rc = conv2d_fwd_args(args[i], it.dtype, it.x, it.w, it.shift, nullptr, it.res, it.y, it.B, it.H, it.W, it.Cin, it.Ho, it.Wo, it.Cout,
+                                 it.kh, it.kw, it.stride, it.pad, it.relu);
+        if (rc) return rc;
+        // fp32 and the layers that the row-sharing / streaming kernels take (3x3 / stride 1) keep their own launches
+        if (on && it.dtype != DCF_F32 && !use_rs(it.dtype, it.kh, it.kw, it.stride, it.pad)) key[i] = igemm_group_key(it.dtype, args[i]);
+    }
+    static const char *const base[3] = {"conv_fwd_grp_f32", "conv_fwd_grp_bf16", "conv_fwd_grp_f16"};
+    return igemm_group_issue<false>(args, key, base, S(stream), [&](int i) {
+        const dcf_conv_fwd_item &it = items[i];
+        return conv2d_fwd_impl(it.dtype, it.x, it.w, it.shift, nullptr, it.res, it.y, it.B, it.H, it.W, it.Cin, it.Ho, it.Wo, it.Cout, it.kh, it.kw,
+                               it.stride, it.pad, it.relu, stream);
+    });
+}
+
+extern "C" int dcf_conv2d_dgrad_group(const dcf_conv_dgrad_item *items, int n, dcf_stream_t stream)
+{
+    DCF_REQUIRE(items && n >= 0, "dcf_conv2d_dgrad_group: bad arguments");
+    std::vector<ConvArgs> args(n);
+    std::vector<int> key(n, -1);
+    const bool on = igemm_group_on();
+    for (int i = 0; i < n; ++i) {
+        const dcf_conv_dgrad_item &it = items[i];
+        int rc = conv2d_dgrad_args(args[i], it.dtype, it.gy, it.wt, it.res, nullptr, it.mask, it.gx, it.B, it.H, it.W, it.Cin, it.Ho, it.Wo, it.Cout,
+                                   it.kh, it.kw, it.stride, it.pad);
+        if (rc) return rc;
+        // stride-2 input gradients (parity classes, the zero-storing 1x1 form) keep their own launches too
+        if (on && it.dtype != DCF_F32 && it.stride == 1 && !args[i].parity && !use_rs(it.dtype, it.kh, it.kw, it.stride, it.pad))
+            key[i] = igemm_group_key(it.dtype, args[i]);
+    }
+    static const char *const base[3] = {"conv_dgrad_grp_f32", "conv_dgrad_grp_bf16", "conv_dgrad_grp_f16"};
+    return igemm_group_issue<true>(args, key, base, S(stream), [&](int i) {
+        const dcf_conv_dgrad_item &it = items[i];
+        return conv2d_dgrad_impl(it.dtype, it.gy, it.wt, it.res, nullptr, it.mask, it.gx, it.B, it.H, it.W, it.Cin, it.Ho, it.Wo, it.Cout, it.kh,
+                                 it.kw, it.stride, it.pad, stream);
+    });
 }
 
 static void wgrad_tiles(int Cin, int Cout, int &TM, int &TN) { TM = Cout >= 64 ? 2 : 1; TN = Cin >= 64 ? 2 : 1; }

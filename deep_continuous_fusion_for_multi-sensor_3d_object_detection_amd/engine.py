@@ -31,6 +31,25 @@ FUSED_SITE_MASK = os.environ.get("DCF_FUSED_SITE_MASK", "1") != "0"
 HALFRES_SHORTCUT = os.environ.get("DCF_HALFRES_SHORTCUT", "1") != "0"
 
 
+# sites whose independent convolutions are handed to the backend together (conv_fwd_group / conv_dgrad_group: one launch per
+# kernel instantiation instead of one per layer; same values).  Bit mask, for A/B runs of single sites: 1 = stage heads (shortcut +
+# conv1), 2 = LiDAR FPN laterals, 4 = camera FPN laterals, 8 = the sites' fc1_feat products, 16 / 32 = the LiDAR / camera FPN
+# laterals' input gradients.
+GROUP_SITES = int(os.environ.get("DCF_GROUP_SITES", "63"))
+
+
+def conv_fwd_group(K, specs, site):
+    """[(layer, x, res, relu[, nxt]), ...] -> outputs in order; one call when the backend groups and the site is switched on."""
+    f = getattr(K, "conv_fwd_group", None) if (GROUP_SITES & site) else None
+    return f(specs) if f is not None else [K.conv_fwd(*s) for s in specs]
+
+
+def conv_dgrad_group(K, specs, site):
+    """[(layer, gy, in_shape, res, mask), ...] -> input gradients in order."""
+    f = getattr(K, "conv_dgrad_group", None) if (GROUP_SITES & site) else None
+    return f(specs) if f is not None else [K.conv_dgrad(*s) for s in specs]
+
+
 class ConvLayer(object):
     """One convolution (or linear = 1x1) of the plan = one row of the dcf_conv_param table."""
 
@@ -101,8 +120,12 @@ class Block(object):
         self.next_conv = None          # conv1 of the block that consumes this block's output (same stage), if any
 
     def forward(self, K, x, save=True):
-        r = K.conv_fwd(self.down, x, None, False) if self.down is not None else x
-        y1 = K.conv_fwd(self.conv1, x, None, True, self.conv2)
+        if self.down is not None:
+            # the shortcut and conv1 read the same x and nothing of each other; the 9-tap member's workgroups go first, the
+            # 1-tap member's short ones fill the tail
+            y1, r = conv_fwd_group(K, [(self.conv1, x, None, True, self.conv2), (self.down, x, None, False)], 1)
+        else:
+            r, y1 = x, K.conv_fwd(self.conv1, x, None, True, self.conv2)
         y = K.conv_fwd(self.conv2, y1, r, True, self.next_conv)
         x._f8 = y1._f8 = None          # fp8 images (fp8 path) are dead once their consumers ran
         self.saved = (x, y1, y) if save else None
@@ -165,8 +188,10 @@ def blocks_forward(K, blocks, x, save=True):
         return x
     specs, ins = [], []                   # per chain layer: (layer, residual, relu); ins[k] = block k's input (tensor or chain index)
     if strided:
-        r = K.conv_fwd(b0.down, x, None, False) if b0.down is not None else x
-        y1 = K.conv_fwd(b0.conv1, x, None, True)
+        if b0.down is not None:
+            y1, r = conv_fwd_group(K, [(b0.conv1, x, None, True), (b0.down, x, None, False)], 1)
+        else:
+            r, y1 = x, K.conv_fwd(b0.conv1, x, None, True)
         x0 = y1                            # the chain's input
         specs.append((b0.conv2, r, True))
         first = 1
@@ -543,10 +568,9 @@ class Plan(object):
                 x = self._fusion_forward(K, self.fusion[si - 1], x, fmap, geom, si - 1, save)
             outs.append(x)
         x1, x2, x3, x4 = outs
-        l1 = K.conv_fwd(self.latconv1, x3, None, False)
-        d1 = K.conv_fwd(self.downconv1, x4, None, False)
+        # the three lateral 1x1 convolutions only read the stage outputs: issued together, then the two resize-and-add passes
+        l1, d1, l2 = conv_fwd_group(K, [(self.latconv1, x3, None, False), (self.downconv1, x4, None, False), (self.latconv2, x2, None, False)], 2)
         t3 = K.resize_fwd(d1, (x3.shape[1], x3.shape[2]), True, l1)      # l1 + up(d1), model.py:161-163
-        l2 = K.conv_fwd(self.latconv2, x2, None, False)
         t2 = K.resize_fwd(t3, (x2.shape[1], x2.shape[2]), True, l2)      # model.py:164-166
         xp = K.conv_fwd(self.conv3, t2, None, False)
         head = K.conv_fwd(self.heads, xp, None, False)
@@ -577,14 +601,14 @@ class Plan(object):
         gxp = K.conv_dgrad(self.heads, ghead, tuple(c["xp"].shape), None)
         K.conv_wgrad(self.conv3, c["t2"], gxp)
         gt2 = K.conv_dgrad(self.conv3, gxp, tuple(c["t2"].shape), None)
-        K.conv_wgrad(self.latconv2, c["x2"], gt2)
-        gx2 = K.conv_dgrad(self.latconv2, gt2, tuple(c["x2"].shape), None)
+        # both resize gradients first, then the three laterals' input gradients, which only read them, together
         gt3 = K.resize_bwd(gt2, c["t3_hw"], True)
-        K.conv_wgrad(self.latconv1, c["x3"], gt3)
-        gx3 = K.conv_dgrad(self.latconv1, gt3, tuple(c["x3"].shape), None)
         gd1 = K.resize_bwd(gt3, c["d1_hw"], True)
+        K.conv_wgrad(self.latconv2, c["x2"], gt2)
+        K.conv_wgrad(self.latconv1, c["x3"], gt3)
         K.conv_wgrad(self.downconv1, c["x4"], gd1)
-        g = K.conv_dgrad(self.downconv1, gd1, tuple(c["x4"].shape), None)
+        gx2, gx3, g = conv_dgrad_group(K, [(self.latconv2, gt2, tuple(c["x2"].shape), None, None), (self.latconv1, gt3, tuple(c["x3"].shape), None, None),
+                                           (self.downconv1, gd1, tuple(c["x4"].shape), None, None)], 16)
         extras = {3: gx3, 2: gx2}          # gradient joining the output of stage index 3 / 2
         gF = None
         masked = False
@@ -631,10 +655,11 @@ class Plan(object):
             x = blocks_forward(K, blocks, x, save)
             feats.append(x)
         c2, c3, c4, c5 = feats
-        p = K.conv_fwd(self.img_lat[3], c5, None, False)
-        for i in (2, 1, 0):
-            lat = K.conv_fwd(self.img_lat[i], feats[i], None, False)
-            p = K.resize_fwd(p, (feats[i].shape[1], feats[i].shape[2]), False, lat)
+        # the four laterals only read the trunk's outputs: issued together, then the chain of resize-and-add passes
+        lats = conv_fwd_group(K, [(self.img_lat[i], feats[i], None, False) for i in (3, 2, 1, 0)], 4)
+        p = lats[0]
+        for k, i in enumerate((2, 1, 0)):
+            p = K.resize_fwd(p, (feats[i].shape[1], feats[i].shape[2]), False, lats[k + 1])
             if i == 0:
                 p2 = p
         fmap = K.conv_fwd(self.img_smooth, p2, None, False)
@@ -648,13 +673,14 @@ class Plan(object):
         g = K.cast_like(gF, im["p2"])                      # fp32 accumulator -> compute dtype
         K.conv_wgrad(self.img_smooth, im["p2"], g)
         gp = K.conv_dgrad(self.img_smooth, g, tuple(im["p2"].shape), None)
-        gfeat = [None] * 4
+        # the chain of resize gradients first, then the four laterals' input gradients, which only read its links, together
+        gps = [gp]
         for i in (0, 1, 2):
-            K.conv_wgrad(self.img_lat[i], feats[i], gp)
-            gfeat[i] = K.conv_dgrad(self.img_lat[i], gp, tuple(feats[i].shape), None)
-            gp = K.resize_bwd(gp, (feats[i + 1].shape[1], feats[i + 1].shape[2]), False)
-        K.conv_wgrad(self.img_lat[3], feats[3], gp)
-        g = K.conv_dgrad(self.img_lat[3], gp, tuple(feats[3].shape), None)
+            gps.append(K.resize_bwd(gps[i], (feats[i + 1].shape[1], feats[i + 1].shape[2]), False))
+        for i in range(4):
+            K.conv_wgrad(self.img_lat[i], feats[i], gps[i])
+        gfeat = conv_dgrad_group(K, [(self.img_lat[i], gps[i], tuple(feats[i].shape), None, None) for i in range(4)], 32)
+        g = gfeat[3]
         masked = False
         for li in range(3, -1, -1):
             g, masked = blocks_backward(K, self.img_stages[li], g, masked, gfeat[li - 1] if li > 0 else None,
@@ -679,7 +705,16 @@ class Plan(object):
             fp = K.point_sample_fwd(fmap, geom["uv"], geom["cnt"], n_max)        # [B,n_max,Cf]
             if save:
                 self.ctx["fuse_fp"] = fp
-        P = K.conv_fwd(f["fc1_feat"], fp.view(B, n_max, 1, fp.shape[-1]), None, False).view(B, n_max, cb)
+        fp4 = fp.view(B, n_max, 1, fp.shape[-1])
+        if save and (GROUP_SITES & 8) and getattr(K, "conv_fwd_group", None) is not None:
+            # every site's fc1_feat product reads the same point features: all of them at the first site reached, kept for the rest
+            Ps = self.ctx.get("fuse_P")
+            if Ps is None:
+                rest = list(range(site, len(self.fusion)))
+                Ps = self.ctx["fuse_P"] = dict(zip(rest, K.conv_fwd_group([(self.fusion[s]["fc1_feat"], fp4, None, False) for s in rest])))
+            P = Ps.pop(site).view(B, n_max, cb)
+        else:
+            P = K.conv_fwd(f["fc1_feat"], fp4, None, False).view(B, n_max, cb)
         hsum, cnt = K.fusion_gather_fwd(P, geom["xyz"], geom["idx"][site], f["stride"], geom["aff"], f["w1d_off"], f["b1_off"])
         out = K.conv_fwd_rowscale(f["fc2"], hsum, x, cnt, f["b2_off"])           # x + hsum.W2^T + cnt*b2 (one epilogue)
         if save:

@@ -191,6 +191,30 @@ int dcf_conv2d_dgrad(int dtype, const void *gy, const void *wt, const void *res,
 int dcf_conv2d_dgrad_halfres(int dtype, const void *gy, const void *wt, const void *res, const void *resq,
                              const void *mask, void *gx, int B, int H, int W, int Cin, int Ho, int Wo, int Cout,
                              int kh, int kw, int stride, int pad, dcf_stream_t stream);
+/* Several INDEPENDENT forward convolutions / input gradients in one call (HOST arrays; no item may read or overwrite what another
+ * item writes).  Items that the generic implicit-GEMM kernel would run with the same instantiation (dtype, K chunk, tile) share
+ * one launch, up to 4 layers each: every layer keeps its own workgroups and its own arithmetic, so each result is bit for bit
+ * what dcf_conv2d_fwd / dcf_conv2d_dgrad write; what is saved is the kernel boundary between small launches.  Everything else
+ * -- fp32, 3x3 / stride-1 layers (they have kernels of their own), stride-2 input gradients, a bucket of one, an instantiation
+ * without a grouped form -- goes through the single-layer entry points inside the call.  Option "IGEMM_GROUP" = "0": every item
+ * takes its single-layer launch.  Fields as the arguments of dcf_conv2d_fwd / dcf_conv2d_dgrad. */
+typedef struct {
+    int32_t dtype, relu;
+    const void *x, *w;
+    const float *shift;        /* may be NULL */
+    const void *res;           /* may be NULL */
+    void *y;
+    int32_t B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, pad_;
+} dcf_conv_fwd_item;
+typedef struct {
+    int32_t dtype, pad_;
+    const void *gy, *wt;
+    const void *res, *mask;    /* may be NULL */
+    void *gx;
+    int32_t B, H, W, Cin, Ho, Wo, Cout, kh, kw, stride, pad, pad2_;
+} dcf_conv_dgrad_item;
+int dcf_conv2d_fwd_group(const dcf_conv_fwd_item *items, int n, dcf_stream_t stream);
+int dcf_conv2d_dgrad_group(const dcf_conv_dgrad_item *items, int n, dcf_stream_t stream);
 /* ---- A CHAIN of 3x3 / stride-1 / pad-1 layers with C channels in and out, each reading the one before it, in ONE launch
  * (csrc/conv_rs.hip, chain mode): the bodies of a residual stage -- /root/reference/model.py:32-41, conv1 -> bn1 -> relu ->
  * conv2 -> bn2 -> += shortcut -> relu, block after block (model.py:48-60) -- forward, or (flip = 1, weights = the
