@@ -8,8 +8,9 @@ the device needs are rounded ONCE to fp32 and are the transform from then on:
 
 Everything else -- the projection matrix that keeps an augmented point on the pixel of its original (compose_crt), the labels
 (transform_boxes) -- is derived from those fp32 values, i.e. from what csrc/geometry.hip's k_augment_points_b really applies.
-The image is never touched: `uv` stays the un-augmented frame's, while the voxel grid, the KNN neighbourhoods, the fusion MLP's
-offsets and the labels move together.
+This block never touches the image: `uv` stays the un-augmented frame's, while the voxel grid, the KNN neighbourhoods, the fusion
+MLP's offsets and the labels move together.  (The camera side has a block of its own, augment_image.py, which moves `uv` along
+with the image instead; the two compose.)
 
 All numpy, no state: draw() is a pure function of (config, seed, rank, call, frame), in the style of the loss sampler's hash
 (loss.py: _mix64 / LossTotal._step_seed), so a resumed or a data-parallel run draws what an uninterrupted one draws, and ranks

@@ -488,6 +488,39 @@ def augment_points_batch(pts_list, params, out_list=None):
     return out_list
 
 
+def augment_image_batch(img_u8, params, out=None):
+    """Train-time camera image augmentation (augment_image.py) of the frames of a batch: img_u8 = a contiguous
+    uint8 device tensor [B,3,H,W] (a view at any byte offset of a larger buffer included), params = B augment_image.draw results;
+    out: a contiguous uint8 [B,3,H,W] tensor to write into (None = a new one).  It must not overlap the input -- the kernel
+    gathers neighbours -- ValueError.  Bit for bit augment_image.transform_image per frame.  One launch per 8 frames.  Returns out."""
+    from . import augment_image
+    for name, t in (("img_u8", img_u8), ("out", out)):
+        if t is None and name == "out":
+            continue
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+            raise H.DcfError("augment_image_batch: %s must be a contiguous uint8 CUDA tensor" % name)
+    if img_u8.dim() != 4 or img_u8.shape[1] != 3 or img_u8.numel() == 0:
+        raise H.DcfError("augment_image_batch: image must be [B,3,H,W] (got %s)" % (tuple(img_u8.shape),))
+    B, _, Hh, Ww = (int(v) for v in img_u8.shape)
+    if len(params) != B:
+        raise H.DcfError("augment_image_batch: %d frames, %d parameter sets" % (B, len(params)))
+    for p in params:                                 # drawn for another image size: the centre would move
+        if (p.get("width", Ww), p.get("height", Hh)) != (Ww, Hh):
+            raise H.DcfError("augment_image_batch: parameters of a %d x %d image for a %d x %d one" % (p["width"], p["height"], Ww, Hh))
+    if out is None:
+        out = torch.empty_like(img_u8)
+    if tuple(out.shape) != tuple(img_u8.shape) or out.device != img_u8.device:
+        raise H.DcfError("augment_image_batch: out must be %s on the image's device" % (tuple(img_u8.shape),))
+    nbytes = img_u8.numel()
+    if img_u8.data_ptr() < out.data_ptr() + nbytes and out.data_ptr() < img_u8.data_ptr() + nbytes:
+        raise ValueError("augment_image_batch: out overlaps the input (the kernel gathers neighbouring pixels)")
+    for b0 in range(0, B, 8):
+        k = min(b0 + 8, B) - b0
+        q = np.ascontiguousarray(np.stack([augment_image.vector8(p) for p in params[b0:b0 + k]], 0), dtype=np.float32)
+        H.call("dcf_augment_image_batch", img_u8[b0:b0 + k], k, Hh, Ww, q, out[b0:b0 + k], H.stream_ptr())
+    return out
+
+
 def knn_bev(xyz, cnt, K, h, w, stride, aff, rmax=None, ws=None, out=None):
     """out: optional int32 [K,h,w] tensor to write into (e.g. a frame's slice of a batch tensor)."""
     n_max = xyz.shape[0]

@@ -158,6 +158,67 @@ def parse_augment_config(config):
     return {"seed": int(seed), "rotation_deg": rot, "scale": scale, "flip_prob": flip, "point_drop": drop}
 
 
+IMAGE_AUGMENT_KEYS = ("enabled", "seed", "zoom", "shift", "flip_prob", "brightness", "contrast", "channel_gain", "drop_prob")
+
+
+def parse_image_augment_config(config):
+    """The `augment_image` block (augment_image.py), validated like `augment`: None = off (no block, or
+    enabled: false), else {"seed", "zoom": (lo, hi), "shift": (fx, fy), "flip_prob", "brightness": (lo, hi), "contrast": (lo, hi),
+    "channel_gain": (lo, hi), "drop_prob"}.  Bad values raise ValueError whether the block is enabled or not.  zoom needs
+    lo >= 0.5: the two-tap bilinear of the kernel covers every source pixel only up to a 2x minification (a bound derived from
+    the filter's footprint, not a measured one)."""
+    import math
+    blk = config.get("augment_image", None)
+    if blk is None:
+        return None
+    if not isinstance(blk, dict):
+        raise ValueError("augment_image must be a mapping (got %r)" % (blk,))
+    unknown = sorted(set(blk) - set(IMAGE_AUGMENT_KEYS))
+    if unknown:
+        raise ValueError("augment_image: unknown keys %s (known: %s)" % (unknown, list(IMAGE_AUGMENT_KEYS)))
+
+    def number(key, v):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError("augment_image.%s must be a number (got %r)" % (key, v))
+        if not math.isfinite(float(v)):
+            raise ValueError("augment_image.%s must be finite (got %r)" % (key, v))
+        return float(v)
+
+    def pair(key, default):
+        v = blk.get(key, default)
+        if not isinstance(v, (list, tuple)) or len(v) != 2:
+            raise ValueError("augment_image.%s must be a pair (got %r)" % (key, v))
+        return number(key, v[0]), number(key, v[1])
+
+    def interval(key, least=None):
+        lo, hi = pair(key, (1.0, 1.0))
+        if lo > hi:
+            raise ValueError("augment_image.%s: lo > hi (got %r)" % (key, blk.get(key)))
+        if lo <= 0.0 or (least is not None and lo < least):
+            raise ValueError("augment_image.%s must be %s (got %r)" % (key, "positive" if least is None else ">= %g" % least, blk.get(key)))
+        return lo, hi
+
+    def probability(key):
+        v = number(key, blk.get(key, 0.0))
+        if not 0.0 <= v <= 1.0:
+            raise ValueError("augment_image.%s must be a probability in [0, 1] (got %r)" % (key, v))
+        return v
+
+    enabled = blk.get("enabled", False)
+    if not isinstance(enabled, bool):
+        raise ValueError("augment_image.enabled must be true or false (got %r)" % (enabled,))
+    seed = blk.get("seed", 0)
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise ValueError("augment_image.seed must be an integer (got %r)" % (seed,))
+    zoom = interval("zoom", least=0.5)
+    shift = pair("shift", (0.0, 0.0))
+    if not (0.0 <= shift[0] <= 0.5 and 0.0 <= shift[1] <= 0.5):
+        raise ValueError("augment_image.shift: fractions of the width and height in [0, 0.5] (got %r)" % (blk.get("shift"),))
+    out = {"seed": int(seed), "zoom": zoom, "shift": shift, "flip_prob": probability("flip_prob"), "brightness": interval("brightness"),
+           "contrast": interval("contrast"), "channel_gain": interval("channel_gain"), "drop_prob": probability("drop_prob")}
+    return out if enabled else None
+
+
 class FlatAdam(object):
     """Adam(lr, betas=(beta1, 0.999), eps=1e-8) of train.py:28 on the flat parameter arena.
     guard (parse_guard_config): the guarded step of csrc/amp.hip -- loss scale, non-finite skip and clipping decided on the
@@ -341,6 +402,11 @@ class Train(nn.Module):
         # (seed, rank, aug_calls, frame) -- no generator state, the count is all a checkpoint has to carry
         self.augment = parse_augment_config(config)
         self.aug_calls = 0
+        # train-time camera image augmentation (augment_image.py; None = off, the default: no buffer, no launch).  It draws from
+        # the same (seed, rank, aug_calls, frame) on hash streams of its own; the augmented image lives in ONE persistent buffer,
+        # written and read on the compute stream
+        self.image_augment = parse_image_augment_config(config)
+        self._aug_image = None
         # the accumulator of gradient accumulation: allocated only when a window holds more than one micro-step
         self.accum_buf = torch.empty_like(self.model.flat_grads.detach()) if self.accum is not None else None
         self._accum_index = 0
@@ -396,7 +462,7 @@ class Train(nn.Module):
             self._geo_sets[key] = st
         return st
 
-    def geometry_async(self, frame_geometry, points_list, crts=None, wait_event=None, augment=None):
+    def geometry_async(self, frame_geometry, points_list, crts=None, wait_event=None, augment=None, image_augment=None):
         """Per-frame geometry (voxelise, project, KNN of the fusion sites) on a side HIP stream, so that these
         small latency-bound kernels overlap the camera stream's convolutions on the compute stream.
         Returns (x_lidar [B,Cz,L,W], geom) where geom carries the events the engine waits on.
@@ -405,6 +471,9 @@ class Train(nn.Module):
         augment: optional per-frame parameters (augment.draw): the side stream first writes the augmented points (dropped ones
         as +inf rows, which every range test rejects) into a persistent buffer of the geometry set, and everything below runs
         on those, with projection matrices that keep every point on the pixel of its original (augment.compose_crt).
+        image_augment: optional per-frame parameters (augment_image.draw) of an image that was zoomed / shifted / flipped: the
+        projection matrices (after the BEV composition) move every point's pixel along (augment_image.compose_crt_image); points
+        that now project outside the image fail the projection kernel's limit test as it is.
         The returned tensors live in one of two persistent buffer sets (config static_geometry, default on): they stay
         valid until the second-next call."""
         main = torch.cuda.current_stream()
@@ -446,6 +515,11 @@ class Train(nn.Module):
                     dst = [torch.empty_like(p) for p in src]
                 points_list = ops.augment_points_batch(src, list(augment), dst)
                 crts = [AUG.compose_crt(frame_geometry.crt if (crts is None or crts[b] is None) else crts[b], augment[b]) for b in range(Bn)]
+            if image_augment is not None:
+                from . import augment_image as AUGI
+                if len(image_augment) != Bn:
+                    raise ValueError("image_augment: %d parameter sets for %d frames" % (len(image_augment), Bn))
+                crts = [AUGI.compose_crt_image(frame_geometry.crt if (crts is None or crts[b] is None) else crts[b], image_augment[b]) for b in range(Bn)]
             if st is not None:
                 x_lidar = st["x_lidar"]
                 st["proj"].zero_()
@@ -642,10 +716,38 @@ class Train(nn.Module):
         """One train step from a FrameLoader batch (raw points + image in HBM): geometry on the side stream, then one_step."""
         batch.wait()
         boxes, nums, params = batch["bboxes"], batch["num_bboxes"], None
+        if self.image_augment is None:             # the step as it is without the image block
+            if self.augment is not None:
+                params, boxes, nums = self._draw_augment(frame_geometry, boxes, nums)
+            x_lidar, geom = self.geometry_async(frame_geometry, batch["points"], crts=batch.get("crt"), wait_event=batch.event, augment=params)
+            self.one_step(x_lidar, batch["image"], boxes, nums, geom=geom)
+            return
+        # both blocks draw from the same call count, which ticks once per step
+        call = self.aug_calls
         if self.augment is not None:
             params, boxes, nums = self._draw_augment(frame_geometry, boxes, nums)
-        x_lidar, geom = self.geometry_async(frame_geometry, batch["points"], crts=batch.get("crt"), wait_event=batch.event, augment=params)
-        self.one_step(x_lidar, batch["image"], boxes, nums, geom=geom)
+        self.aug_calls = call + 1
+        image, iparams = self._augment_image(batch["image"], call)
+        x_lidar, geom = self.geometry_async(frame_geometry, batch["points"], crts=batch.get("crt"), wait_event=batch.event, augment=params,
+                                            image_augment=iparams)
+        self.one_step(x_lidar, image, boxes, nums, geom=geom)
+
+    def _augment_image(self, image, call):
+        """This step's per-frame image parameters (augment_image.draw at `call`) and the augmented uint8 [B,3,H,W] image: one launch
+        on the compute stream -- the stream of its consumer, so no events -- into the trainer's one persistent buffer (allocated
+        on first use, re-made when the shape changes).  Outside the captured graphs: a replay copies it into its static image
+        buffer as it does any image."""
+        from . import augment_image as AUGI
+        if image.dtype != torch.uint8 or image.dim() != 4 or not image.is_cuda:
+            raise ValueError("augment_image needs the batch's image as a uint8 [B,3,H,W] device tensor (got %s %s)" % (image.dtype, tuple(image.shape)))
+        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        Bn, _, Hh, Ww = (int(v) for v in image.shape)
+        cfg = self.image_augment
+        iparams = [AUGI.draw(cfg, cfg["seed"], rank, call, b, Ww, Hh) for b in range(Bn)]
+        if self._aug_image is None or self._aug_image.shape != image.shape or self._aug_image.device != image.device:
+            self._aug_image = torch.empty(tuple(image.shape), dtype=torch.uint8, device=image.device)
+        ops.augment_image_batch(image.contiguous(), iparams, self._aug_image)
+        return self._aug_image, iparams
 
     def _draw_augment(self, frame_geometry, boxes, nums):
         """This step's per-frame augmentation parameters and the labels under them (host tensors of max_num_bbox rows: no device

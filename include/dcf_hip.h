@@ -110,6 +110,16 @@ int dcf_project_filter_batch(const float *const *pts, const int *n, int B, const
 int dcf_augment_points_batch(const float *const *pts, const int *n, int B, const float *mat, const uint64_t *drop_key,
                              const uint32_t *drop_thresh, float *const *out, dcf_stream_t stream);
 
+/* Train-time camera image augmentation of the B (<= 8) frames of a batch in one launch (host statement:
+ * augment_image.py).  img / out: device uint8 [B][3][H][W], contiguous, ANY byte alignment (a view into a larger buffer is fine),
+ * 3 H W <= 2^30; out must not overlap img (the kernel gathers neighbours; refused).  q HOST float[B][8] = {ku, cu, kv, cv, g0,
+ * g1, g2, bias}, finite: the inverse of the image-plane affine u' = u / ku - cu / ku (likewise v) and the photometric line, each
+ * rounded once to fp32.  For the output pixel (h, w), every operation rounded to fp32, nothing contracted:
+ *   fx = ((ku (w + .5)) + cu) - .5   x0 = floor(fx)   wx = fx - x0        (fy, y0, wy from h, kv, cv)
+ *   top = p00 (1 - wx) + p01 wx   bot likewise   val = top (1 - wy) + bot wy   t = g_c val + bias
+ *   out = clamp(rint(t), 0, 255), round half to even; a tap outside the image contributes 0. */
+int dcf_augment_image_batch(const uint8_t *img, int B, int H, int W, const float *q, uint8_t *out, dcf_stream_t stream);
+
 /* BEV K-nearest-neighbour (reference: model.py:199-203 TODO; spec SURVEY.md App. D).
  * xyz [n_max][3], first *count_dev rows valid.  idx_out int32 [K][h][w], -1 padding.
  * rmax2 < 0 = unbounded.  K <= 8.  ws: dcf_knn_workspace_bytes(n_max,h,w). */
