@@ -226,8 +226,12 @@ __global__ void __launch_bounds__(256) k_resize_bwd(const T *gy, T *gx, int B, i
     const int b = (int)(p / Hi);
     const int C = CV * V;
     const float inv_h = sh > 0.f ? 1.f / sh : (float)Ho, inv_w = sw > 0.f ? 1.f / sw : (float)Wo;
-    int oh_lo = (int)floorf(((float)ih - 1.f) * inv_h) - 2, oh_hi = (int)ceilf(((float)ih + 1.f) * inv_h) + 2;
-    int ow_lo = (int)floorf(((float)iw - 1.f) * inv_w) - 2, ow_hi = (int)ceilf(((float)iw + 1.f) * inv_w) + 2;
+    // outputs that reach input i: s(o) < i + 1, i.e. o < (i + 1) / scale with align_corners and o < (i + 1.5) / scale - 0.5 under the
+    // half-pixel rule (the extra half input pixel is 4 outputs at x8: more than the margin of 2, which is there for rounding; at x2
+    // the window is the one ceil((i + 1) / scale) + 2 gave)
+    int oh_lo = (int)floorf(((float)ih - 1.f) * inv_h) - 2, ow_lo = (int)floorf(((float)iw - 1.f) * inv_w) - 2;
+    int oh_hi = (align ? (int)ceilf(((float)ih + 1.f) * inv_h) : (int)floorf(((float)ih + 1.5f) * inv_h - 0.5f)) + 2;
+    int ow_hi = (align ? (int)ceilf(((float)iw + 1.f) * inv_w) : (int)floorf(((float)iw + 1.5f) * inv_w - 0.5f)) + 2;
     oh_lo = max(oh_lo, 0); oh_hi = min(oh_hi, Ho - 1);
     ow_lo = max(ow_lo, 0); ow_hi = min(ow_hi, Wo - 1);
     float acc[V];

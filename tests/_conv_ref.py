@@ -199,6 +199,14 @@ def wgrad_reference(shape):
     return d, G, gs
 
 
+def image_nhwc4(img):
+    """img uint8 [B,3,H,W] -> fp64 [B,H+6,W+8,4], the layout of dcf_image_to_nhwc4: x / 255 with a halo of 3, channels padded to 4."""
+    B, _, H, W = img.shape
+    x4 = torch.zeros((B, H + 6, W + 8, 4), dtype=torch.float64)
+    x4[:, 3:3 + H, 3:3 + W, :3] = (img.double() / 255.0).permute(0, 2, 3, 1)
+    return x4
+
+
 @functools.lru_cache(maxsize=4)
 def stem_reference(shape, dtype):
     """shape = (B, H, W, Cout): the 7x7 / stride-2 / pad-3 stem on a 0 / 255 image.  -> (inputs, exact plain conv, exact
@@ -212,8 +220,8 @@ def stem_reference(shape, dtype):
     assert_accumulator_exact(lin, 2 * 147)
     Ho, Wo = out_size(H, 7, 2, 3), out_size(W, 7, 2, 3)
     gy = ints((B, Ho, Wo, Cout), -3, 3, 4003)
-    x4 = torch.zeros((B, H + 6, W + 8, 4), dtype=torch.float64)        # dcf_image_to_nhwc4: halo of 3, channels padded to 4
-    x4[:, 3:3 + H, 3:3 + W, :3] = x
+    x4 = image_nhwc4(img)
+    assert torch.equal(x4[:, 3:3 + H, 3:3 + W, :3], x)
     G, gs = wgrad_taps(x4, gy, 7, 8, 2)
     assert_accumulator_exact(G, 3 * B * Ho * Wo)
     return dict(img=img, w=w, shift=shift, gy=gy), lin, conv_fwd(x, w, 2, 3, shift, None, None, True), G, gs
