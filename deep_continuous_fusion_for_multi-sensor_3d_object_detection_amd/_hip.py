@@ -146,6 +146,12 @@ SIGNATURES = {
                                        c_int, c_int, c_float, c_float, c_float, c_float, c_int, P, P, c_i64, P, c_i64, P, P, P]),
     "dcf_loss_focal_fwd_bwd_det": (c_int, [P, c_i64, P, c_i64, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float,
                                            c_int, c_int, c_float, c_float, c_float, c_float, c_int, P, P, c_i64, P, c_i64, P, P, P]),
+    # loss_sampling: anchor (IoU-based anchor assignment and the terms on its targets; csrc/loss.hip, k_assign_* / k_loss_anchor)
+    "dcf_assign_anchors_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dcf_assign_anchors_iou": (c_int, [P, P, P, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_double, P, P, P, P, P]),
+    "dcf_loss_anchor_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dcf_loss_anchor_fwd_bwd": (c_int, [P, c_i64, P, c_i64, P, P, c_int, c_int, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_int,
+                                        P, P, c_i64, P, c_i64, P, P, P]),
     "dcf_adam_step": (c_int, [P, P, P, P, c_i64, c_float, c_float, c_float, c_float, c_int, c_float, P]),
     "dcf_grad_stats": (c_int, [P, c_i64, P, P]),
     "dcf_amp_update": (c_int, [P, c_float, c_int, ctypes.c_double, ctypes.c_double, c_int, c_float, c_float, c_float, c_float, P]),

@@ -1,4 +1,5 @@
 // loss.hip -- the device half of the detection objective (loss.py:129-189 of the reference).
+// (Further down: the device sampler, hard negative mining, the dense focal term and the IoU-based anchor assignment.)
 //
 // Target assignment stays on the host (it consumes numpy's global RNG exactly like loss.py:74-127); what runs here is
 // everything that touches the head outputs: the 2-way cross-entropy at the sampled positive / negative cells of both
@@ -6,6 +7,7 @@
 // (loss.py:144-186) -- and their gradients, written straight into dense gradient maps.  One launch replaces the ~60 tiny
 // gather / softmax / index_put kernels of the vectorised torch version.
 #include "dcf_common.h"
+#include "ev_geom.h"        // the evaluation's fp64 rectangle clip: the anchor assignment's IoU
 
 namespace {
 
@@ -752,6 +754,271 @@ __global__ void k_focal_fold(const float *ws, int B, int b0, int G, float gain, 
     *loss = (float)tot;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// IoU-based anchor assignment ("loss_sampling: anchor"; assign.py is the host statement).  Anchor index
+// j = a * HW + cell; I(j, k) = ev_bev_iou(anchor j's rectangle, label k's) in fp64 (ev_geom.h: the evaluation's clip), 0 for a void label
+// (a non-finite x, y, l, w or yaw, or l <= 0 or w <= 0).  best(j) = max_k I, arg(j) the lowest k attaining it; forced(k) = the j of highest
+// I(j, k) when that is > 0, ties to the lowest j.  target(j) = the lowest k with forced(k) == j, else arg(j) when best >= pos_iou, else -1
+// (negative) when best < neg_iou, else -2 (ignored).
+//
+// A pair whose centres lie further apart than the two half-diagonals together (times AS_PRUNE) skips the clip: the rectangles are
+// disjoint and the clip's own value is exactly 0.  Almost every pair goes that way; the 592 B of scratch the clip costs each lane are
+// touched by the few lanes near a label.
+//   k_assign_force   AS_SEG workgroups per (label, sample), each over a contiguous range of the 2 HW anchors: arg-max through LDS on
+//                    (IoU bits, lower j) -- non-negative doubles order like their bit patterns; the partial goes to its own slot
+//   k_assign_dense   one thread per cell, both anchors, the sample's labels staged in LDS as fp64 -- and forced(k), folded from the
+//                    label's AS_SEG partials in range order; stores target (and best), the workgroup's integer counts go to its own
+//                    workspace slot
+//   k_assign_fold    adds the slots of a sample, one wave per sample: counts [B][4] = (positives N_b, ignored, positive through forcing only, void labels)
+// Integer and fp64 work in a fixed order, no atomics: one entry serves deterministic: true and false.
+constexpr int AS_THREADS = 256;
+constexpr int AS_SEG = 16;                      // anchor ranges per label in k_assign_force (one workgroup per label left 24 of them
+                                                // busy at cfg2: 238 us)
+constexpr double AS_PRUNE = 1.002;              // on the squared distance: 0.1 % of slack on the distance, against 1e-16 of rounding
+
+// workspace: the partial arg-max values, u64 [B][max_box][AS_SEG]; their anchors, int [B][max_box][AS_SEG]; the count slots, int [B][G][4]
+inline int64_t assign_ws_ints(int B, int HW, int max_box) { return (int64_t)B * max_box * AS_SEG * 3 + (int64_t)B * cdiv(HW, AS_THREADS) * 4; }
+
+struct AssignArgs {
+    const float *anc, *boxes;
+    const int32_t *nbox;
+    int32_t *target, *counts, *part_j, *slots;
+    unsigned long long *part_v;
+    double *best;
+    double pos_iou, neg_iou;
+    int max_box, box_stride, B, HW, G;
+};
+
+__device__ __forceinline__ bool label_void(const float *bx)
+{
+    return !(isfinite(bx[0]) && isfinite(bx[1]) && isfinite(bx[3]) && isfinite(bx[4]) && isfinite(bx[6]) && bx[3] > 0.f && bx[4] > 0.f);
+}
+__device__ __forceinline__ double half_diag(double l, double w) { return 0.5 * sqrt(l * l + w * w); }
+// the seven parameters of anchor (a, cell), gathered from [2][7][HW]
+__device__ __forceinline__ void anchor_row(const float *anc, int a, int cell, int HW, float (&row)[7])
+{
+#pragma unroll
+    for (int c = 0; c < 7; ++c) row[c] = anc[((int64_t)a * 7 + c) * HW + cell];
+}
+
+__global__ void __launch_bounds__(AS_THREADS) k_assign_force(AssignArgs a)
+{
+    __shared__ unsigned long long s_val[AS_THREADS];
+    __shared__ int s_j[AS_THREADS];
+    const int k = blockIdx.x, b = blockIdx.y, seg = blockIdx.z, tid = threadIdx.x;
+    const int nb = max(min(a.nbox[b], a.max_box), 0);
+    const int64_t slot = ((int64_t)b * a.max_box + k) * AS_SEG + seg;
+    const float *bx = a.boxes + ((int64_t)b * a.max_box + k) * a.box_stride;
+    if (k >= nb || label_void(bx)) {               // (uniform over the workgroup)
+        if (tid == 0) { a.part_v[slot] = 0ull; a.part_j[slot] = -1; }
+        return;
+    }
+    const int per = (int)(((int64_t)2 * a.HW + AS_SEG - 1) / AS_SEG), lo = seg * per, hi = lo + max(min(per, 2 * a.HW - lo), 0);
+    double lab[4][2];
+    ev_rect(bx, lab);
+    const double lx = bx[0], ly = bx[1], lh = half_diag(bx[3], bx[4]);
+    unsigned long long bv = 0ull;                   // bits of the best IoU so far (+0.0), and its anchor
+    int bj = -1;
+    for (int j = lo + tid; j < hi; j += AS_THREADS) {
+        const int an = j >= a.HW ? 1 : 0, cell = j - an * a.HW;
+        float row[7];
+        anchor_row(a.anc, an, cell, a.HW, row);
+        const double dx = (double)row[0] - lx, dy = (double)row[1] - ly, s = half_diag(row[3], row[4]) + lh;
+        if (dx * dx + dy * dy > s * s * AS_PRUNE) continue;
+        double rect[4][2];
+        ev_rect(row, rect);
+        const unsigned long long v = (unsigned long long)__double_as_longlong(ev_bev_iou(rect, lab));
+        if (v > bv && v <= 0x7ff0000000000000ull) { bv = v; bj = j; }      // (j ascends: the first of equal values stays)
+    }
+    s_val[tid] = bv; s_j[tid] = bj;
+    __syncthreads();
+    for (int o = AS_THREADS / 2; o > 0; o >>= 1) {
+        if (tid < o) {
+            const unsigned long long v2 = s_val[tid + o];
+            const int j2 = s_j[tid + o];
+            if (v2 > s_val[tid] || (v2 == s_val[tid] && v2 != 0ull && j2 < s_j[tid])) { s_val[tid] = v2; s_j[tid] = j2; }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) { a.part_v[slot] = s_val[0]; a.part_j[slot] = s_val[0] != 0ull ? s_j[0] : -1; }
+}
+
+__global__ void __launch_bounds__(AS_THREADS) k_assign_dense(AssignArgs a)
+{
+    __shared__ double l_rect[64][4][2];
+    __shared__ double l_x[64], l_y[64], l_h[64];
+    __shared__ int l_ok[64], l_forced[64];
+    __shared__ int s_cnt[AS_THREADS / 64][3];
+    const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    const int nb = max(min(a.nbox[b], a.max_box), 0);           // (the entry checks max_box <= 64)
+    if (tid < nb) {
+        const float *bx = a.boxes + ((int64_t)b * a.max_box + tid) * a.box_stride;
+        const bool ok = !label_void(bx);
+        l_ok[tid] = ok ? 1 : 0;
+        unsigned long long fv = 0ull;                               // forced(tid): the ranges ascend in j, so the first of equal values stays
+        int fj = -1;
+        for (int q = 0; q < AS_SEG; ++q) {
+            const int64_t slot = ((int64_t)b * a.max_box + tid) * AS_SEG + q;
+            if (a.part_v[slot] > fv) { fv = a.part_v[slot]; fj = a.part_j[slot]; }
+        }
+        l_forced[tid] = fj;
+        if (ok) {
+            ev_rect(bx, l_rect[tid]);
+            l_x[tid] = bx[0]; l_y[tid] = bx[1]; l_h[tid] = half_diag(bx[3], bx[4]);
+        }
+    }
+    __syncthreads();
+    const int cell = g * AS_THREADS + tid;
+    int npos = 0, nign = 0, nforced = 0;
+    if (cell < a.HW) {
+#pragma unroll 1
+        for (int an = 0; an < 2; ++an) {
+            const int j = an * a.HW + cell;
+            float row[7];
+            anchor_row(a.anc, an, cell, a.HW, row);
+            const double ax = row[0], ay = row[1], ah = half_diag(row[3], row[4]);
+            double rect[4][2];
+            bool have = false;
+            double best = 0.0;
+            int arg = nb > 0 ? 0 : -1;
+            for (int k = 0; k < nb; ++k) {
+                if (!l_ok[k]) continue;
+                const double dx = ax - l_x[k], dy = ay - l_y[k], s = ah + l_h[k];
+                if (dx * dx + dy * dy > s * s * AS_PRUNE) continue;
+                if (!have) { ev_rect(row, rect); have = true; }
+                const double v = ev_bev_iou(rect, l_rect[k]);
+                if (v > best) { best = v; arg = k; }
+            }
+            int t = -3;
+            for (int k = nb - 1; k >= 0; --k) t = l_forced[k] == j ? k : t;      // the lowest k that forces j
+            if (t >= 0) {
+                nforced += best >= a.pos_iou ? 0 : 1;
+            } else if (best >= a.pos_iou) {
+                t = arg;
+            } else {
+                t = best < a.neg_iou ? -1 : -2;
+            }
+            npos += t >= 0 ? 1 : 0;
+            nign += t == -2 ? 1 : 0;
+            a.target[(int64_t)b * 2 * a.HW + j] = t;
+            if (a.best) a.best[(int64_t)b * 2 * a.HW + j] = best;
+        }
+    }
+    npos = wave_sum_i(npos); nign = wave_sum_i(nign); nforced = wave_sum_i(nforced);
+    if ((tid & 63) == 0) { s_cnt[tid >> 6][0] = npos; s_cnt[tid >> 6][1] = nign; s_cnt[tid >> 6][2] = nforced; }
+    __syncthreads();
+    if (tid == 0) {
+        int32_t *slot = a.slots + ((int64_t)b * a.G + g) * 4;
+        int nvoid = 0;
+        for (int k = 0; k < nb; ++k) nvoid += l_ok[k] ? 0 : 1;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) slot[c] = (s_cnt[0][c] + s_cnt[1][c]) + (s_cnt[2][c] + s_cnt[3][c]);
+        slot[3] = g == 0 ? nvoid : 0;
+    }
+}
+
+// one wave per sample (integer sums: any order gives the same counts)
+__global__ void __launch_bounds__(64) k_assign_fold(const int32_t *slots, int G, int32_t *counts)
+{
+    const int b = blockIdx.x, lane = threadIdx.x;
+    int c[4] = {0, 0, 0, 0};
+    for (int g = lane; g < G; g += 64)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) c[q] += slots[((int64_t)b * G + g) * 4 + q];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) c[q] = wave_sum_i(c[q]);
+    if (lane == 0)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) counts[4 * b + q] = c[q];
+}
+
+// The terms on per-anchor targets: the shape of k_loss_focal -- (G, B) workgroups over contiguous chunks, one thread per cell.  Every
+// cell of a computed sample gets all 4 classification and all 14 regression gradients STORED (zeros where a term is absent): no
+// atomics, no dependence on a zero fill.  A target outside [-2, max_box) counts as ignored.  N_b = counts[b][0].
+// per-sample workspace, in floats: [0, G) the classification partials, [HARD_MAXG, HARD_MAXG + G) the regression partials (both
+// undivided)
+constexpr int AL_STRIDE = 2 * HARD_MAXG;
+
+struct LossAnchorArgs {
+    const float *cls, *reg, *anc, *boxes;
+    const int32_t *target, *counts;
+    int64_t cls_bs, reg_bs, gcls_bs, greg_bs;
+    float *gcls, *greg, *ws;
+    int max_box, box_stride, b0, B, HW, reduction, chunk;
+    float gain, alpha, gamma, eps;
+};
+
+__global__ void __launch_bounds__(HARD_THREADS) k_loss_anchor(LossAnchorArgs a)
+{
+    __shared__ float red[4];
+    const int g = blockIdx.x, b = a.b0 + blockIdx.y, tid = threadIdx.x;
+    const int HW = a.HW;
+    const int npos = max(a.counts[4 * b], 1);
+    const float wsample = sample_weight(a.reduction, a.B);
+    const float gscale = (1.f / (float)npos) * wsample;
+    const float rscale = a.gain * wsample / (7.f * (float)npos);
+    const float *c = a.cls + b * a.cls_bs, *r = a.reg + b * a.reg_bs;
+    const float *bx = a.boxes + (int64_t)b * a.max_box * a.box_stride;
+    const int32_t *tg = a.target + (int64_t)b * 2 * HW;
+    float *gc = a.gcls + b * a.gcls_bs, *gr = a.greg + b * a.greg_bs;
+    const int lo = g * a.chunk, hi = min(lo + a.chunk, HW);
+    float acc = 0.f, accr = 0.f;
+    for (int cell = lo + tid; cell < hi; cell += HARD_THREADS) {
+#pragma unroll
+        for (int an = 0; an < 2; ++an) {
+            int t = tg[(int64_t)an * HW + cell];
+            if (t < -2 || t >= a.max_box) t = -2;
+            const bool y = t >= 0;
+            const float s0 = c[(int64_t)(2 * an) * HW + cell], s1 = c[(int64_t)(2 * an + 1) * HW + cell];
+            float g0 = 0.f, g1 = 0.f;
+            if (t != -2) {
+                const float gq = focal_cell(y ? s1 : s0, y ? a.alpha : 1.f - a.alpha, a.gamma, a.eps, acc) * gscale;
+                g0 = y ? 0.f : gq; g1 = y ? gq : 0.f;
+            }
+            gc[(int64_t)(2 * an) * HW + cell] = g0;
+            gc[(int64_t)(2 * an + 1) * HW + cell] = g1;
+            const float *anp = a.anc + (int64_t)an * 7 * HW + cell;
+            const float *box = bx + (int64_t)(y ? t : 0) * a.box_stride;
+#pragma unroll
+            for (int q = 0; q < 7; ++q) {
+                float gv = 0.f;
+                if (y) {
+                    const float d = r[(int64_t)(7 * an + q) * HW + cell] - reg_target(box, anp, q, HW);
+                    const float ad = fabsf(d);
+                    accr += ad < 1.f ? 0.5f * d * d : ad - 0.5f;
+                    gv = sl1_grad(d) * rscale;
+                }
+                gr[(int64_t)(7 * an + q) * HW + cell] = gv;
+            }
+        }
+    }
+    float *ws = a.ws + (int64_t)b * AL_STRIDE;
+    const float part = block_sum<4>(acc, red);
+    const float partr = block_sum<4>(accr, red);
+    if (tid == 0) { ws[g] = part; ws[HARD_MAXG + g] = partr; }
+}
+
+// loss = sum over the samples that count of wsample * (cls_b + gain * reg_b): one thread, the partials in workgroup order in double,
+// rounded once; terms [B][3] = (cls_b, reg_b, N_b), zero rows for the samples 'last' leaves out
+__global__ void k_anchor_fold(const float *ws, const int32_t *counts, int B, int b0, int G, float gain, float wsample, float *loss, float *terms)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double tot = 0.0;
+    for (int b = 0; b < B; ++b) {
+        float *t = terms + 3 * b;
+        if (b < b0) { t[0] = 0.f; t[1] = 0.f; t[2] = 0.f; continue; }
+        const float *w = ws + (int64_t)b * AL_STRIDE;
+        double s = 0.0, sr = 0.0;
+        for (int g = 0; g < G; ++g) { s += (double)w[g]; sr += (double)w[HARD_MAXG + g]; }
+        const int n = counts[4 * b];
+        const double den = (double)max(n, 1);
+        const double clsv = s / den, regv = sr / (7.0 * den);
+        t[0] = (float)clsv; t[1] = (float)regv; t[2] = (float)n;
+        tot += (double)wsample * (clsv + (double)gain * regv);
+    }
+    *loss = (float)tot;
+}
+
 }  // namespace
 
 extern "C" uint32_t dcf_loss_sample_rand(uint64_t seed, int sample, int stream, int index, int attempt)
@@ -962,5 +1229,72 @@ extern "C" int dcf_loss_fwd_bwd(const float *cls, int64_t cls_bstride, const flo
     hipStream_t s = S(stream);
     DCF_LAUNCH("loss_fwd_bwd", s, hipLaunchKernelGGL(k_loss_fwd_bwd<false>, dim3(B), dim3(1024), 0, s, cls, cls_bstride, reg, reg_bstride, anchors, ints,
                                                      floats, B, HW, reg_gain, reduction, loss, gcls, gcls_bstride, greg, greg_bstride, (float *)nullptr));
+    return DCF_OK;
+}
+
+// loss_sampling: anchor -- the assignment (k_assign_force, k_assign_dense, k_assign_fold) ...
+extern "C" size_t dcf_assign_anchors_workspace_bytes(int B, int H, int W, int max_box)
+{
+    if (B <= 0 || H <= 0 || W <= 0 || max_box < 1 || max_box > 64 || (int64_t)H * W >= (int64_t)1 << 30) return 0;
+    return (size_t)assign_ws_ints(B, H * W, max_box) * sizeof(int32_t);
+}
+
+extern "C" int dcf_assign_anchors_iou(const float *anchors, const float *boxes, const int32_t *nbox_dev, int max_box, int box_stride, int B, int H,
+                                      int W, double pos_iou, double neg_iou, int32_t *target, double *best, int32_t *counts, void *workspace,
+                                      dcf_stream_t stream)
+{
+    DCF_REQUIRE(anchors && boxes && nbox_dev && target && counts && B > 0 && H > 0 && W > 0, "dcf_assign_anchors_iou: bad arguments");
+    DCF_REQUIRE(max_box >= 1 && max_box <= 64 && box_stride >= 7, "dcf_assign_anchors_iou: 1 to 64 boxes per sample, at least 7 values each");
+    DCF_REQUIRE((int64_t)H * W < (int64_t)1 << 30, "dcf_assign_anchors_iou: map too large");
+    DCF_REQUIRE(neg_iou > 0.0 && neg_iou <= pos_iou && pos_iou <= 1.0, "dcf_assign_anchors_iou: 0 < neg_iou <= pos_iou <= 1");
+    DCF_REQUIRE(workspace && ((uintptr_t)workspace & 7) == 0 && (!best || ((uintptr_t)best & 7) == 0), "dcf_assign_anchors_iou: null or misaligned workspace / best");
+    AssignArgs a;
+    a.anc = anchors; a.boxes = boxes; a.nbox = nbox_dev; a.target = target; a.best = best; a.counts = counts;
+    a.part_v = (unsigned long long *)workspace; a.part_j = (int32_t *)(a.part_v + (int64_t)B * max_box * AS_SEG);
+    a.slots = a.part_j + (int64_t)B * max_box * AS_SEG;
+    a.pos_iou = pos_iou; a.neg_iou = neg_iou; a.max_box = max_box; a.box_stride = box_stride; a.B = B; a.HW = H * W;
+    a.G = cdiv(a.HW, AS_THREADS);
+    hipStream_t s = S(stream);
+    DCF_LAUNCH("assign_force", s, hipLaunchKernelGGL(k_assign_force, dim3(max_box, B, AS_SEG), dim3(AS_THREADS), 0, s, a));
+    DCF_LAUNCH_B("assign_dense", (double)B * a.HW * (14.0 * 4 + 2 * 4 + (best ? 16.0 : 0.0)), s,
+                 hipLaunchKernelGGL(k_assign_dense, dim3(a.G, B), dim3(AS_THREADS), 0, s, a));
+    DCF_LAUNCH("assign_fold", s, hipLaunchKernelGGL(k_assign_fold, dim3(B), dim3(64), 0, s, a.slots, a.G, counts));
+    return DCF_OK;
+}
+
+// ... and the terms on its targets (k_loss_anchor over the whole map, then the fold)
+extern "C" size_t dcf_loss_anchor_workspace_bytes(int B, int H, int W)
+{
+    if (B <= 0 || H <= 0 || W <= 0 || (int64_t)H * W >= (int64_t)1 << 30) return 0;
+    return (size_t)B * AL_STRIDE * sizeof(float);
+}
+
+extern "C" int dcf_loss_anchor_fwd_bwd(const float *cls, int64_t cls_bstride, const float *reg, int64_t reg_bstride, const float *anchors,
+                                       const float *boxes, int max_box, int box_stride, const int32_t *target, const int32_t *counts, int B, int H,
+                                       int W, float alpha, float gamma, float eps, float reg_gain, int reduction, float *loss, float *gcls,
+                                       int64_t gcls_bstride, float *greg, int64_t greg_bstride, float *terms, void *workspace, dcf_stream_t stream)
+{
+    DCF_REQUIRE(cls && reg && anchors && boxes && target && counts && loss && gcls && greg && terms && B > 0 && H > 0 && W > 0,
+                "dcf_loss_anchor_fwd_bwd: bad arguments");
+    DCF_REQUIRE(reduction >= 0 && reduction <= 2, "dcf_loss_anchor_fwd_bwd: reduction must be 0 (last), 1 (sum) or 2 (mean)");
+    DCF_REQUIRE(max_box >= 1 && max_box <= 64 && box_stride >= 7, "dcf_loss_anchor_fwd_bwd: 1 to 64 boxes per sample, at least 7 values each");
+    DCF_REQUIRE((int64_t)H * W < (int64_t)1 << 30, "dcf_loss_anchor_fwd_bwd: map too large");
+    DCF_REQUIRE(alpha > 0.f && alpha < 1.f && (gamma == 0.f || gamma >= 1.f) && eps > 0.f && eps <= 1e-3f,
+                "dcf_loss_anchor_fwd_bwd: alpha in (0, 1), gamma 0 or >= 1, eps in (0, 1e-3]");
+    DCF_REQUIRE(workspace && ((uintptr_t)workspace & 3) == 0, "dcf_loss_anchor_fwd_bwd: null or misaligned workspace");
+    const int HW = H * W;
+    LossAnchorArgs a;
+    a.cls = cls; a.reg = reg; a.anc = anchors; a.boxes = boxes; a.target = target; a.counts = counts;
+    a.cls_bs = cls_bstride; a.reg_bs = reg_bstride; a.gcls_bs = gcls_bstride; a.greg_bs = greg_bstride;
+    a.gcls = gcls; a.greg = greg; a.ws = (float *)workspace;
+    a.max_box = max_box; a.box_stride = box_stride; a.B = B; a.HW = HW; a.reduction = reduction; a.chunk = hard_chunk(HW);
+    a.b0 = reduction == 0 ? B - 1 : 0;              // 'last': only the last sample is computed
+    a.gain = reg_gain; a.alpha = alpha; a.gamma = gamma; a.eps = eps;
+    const int G = cdiv(HW, a.chunk);
+    hipStream_t s = S(stream);
+    DCF_LAUNCH_B("loss_anchor_fwd_bwd", (double)(B - a.b0) * HW * 4.0 * 38.0, s,
+                 hipLaunchKernelGGL(k_loss_anchor, dim3(G, B - a.b0), dim3(HARD_THREADS), 0, s, a));
+    DCF_LAUNCH("loss_anchor_fold", s, hipLaunchKernelGGL(k_anchor_fold, dim3(1), dim3(64), 0, s, a.ws, counts, B, a.b0, G, reg_gain,
+                                                          sample_weight(reduction, B), loss, terms));
     return DCF_OK;
 }

@@ -30,7 +30,8 @@ extern "C" const char *dcf_last_error(void) { return g_err; }
 // 202 still: the deterministic-mode entries (dcf_inv_sort_segments, dcf_cam_invert, dcf_point_sample_bwd_det, dcf_fusion_gather_bwd_det,
 // dcf_rowscale_bias_bwd_det, dcf_rows_fold, dcf_loss_fwd_bwd_det, dcf_loss_sample_fwd_bwd_det) and the hard-mining entries
 // (dcf_loss_hard_workspace_bytes, dcf_loss_hard_fwd_bwd, dcf_loss_hard_fwd_bwd_det) and the focal entries (dcf_loss_focal_workspace_bytes,
-// dcf_loss_focal_fwd_bwd, dcf_loss_focal_fwd_bwd_det) were ADDED without a new minor:
+// dcf_loss_focal_fwd_bwd, dcf_loss_focal_fwd_bwd_det) and the anchor-assignment entries (dcf_assign_anchors_workspace_bytes,
+// dcf_assign_anchors_iou, dcf_loss_anchor_workspace_bytes, dcf_loss_anchor_fwd_bwd) were ADDED without a new minor:
 // tests/test_amp_host.py pins 202 exactly.  A binding that needs them asks for the symbols (tests/test_determinism_host.py does).
 extern "C" int dcf_version(void) { return 202; }
 

@@ -21,6 +21,11 @@ alpha_t * (1 - p_t)^gamma and normalised by the number of distinct positive cell
 map, one thread per cell, no atomics in the classification half); the regression rows are those of the other modes.  focal_terms() below
 is the host statement (float64); CPU tensors take it.  LossTotal.last_terms then holds (cls_b, reg_b, |P_b|) per sample.
 
+`loss_sampling: anchor` uses the two anchors of a cell as anchors: every (anchor, cell) pair gets a target of its own by rotated
+bird's-eye IoU with the labels (positive from assign_pos_iou, negative below assign_neg_iou, ignored in between, the best anchor of every
+label forced positive; assign.py is the host statement, csrc/loss.hip k_assign_* the device's), the focal term runs over the anchors
+that are not ignored and the regression over the positive ones (anchor_terms() below; k_loss_anchor).  No windows, nothing drawn.
+
 Reference quirks are kept behind `loss_reduction: last` (default): cross-entropy on already
 soft-maxed scores (loss.py:17-20,139), 129 negatives (:125), only the last sample of the
 batch contributes (:71).  'sum' / 'mean' accumulate over the batch instead.
@@ -173,6 +178,52 @@ def focal_terms(cls_b, P_b, alpha, gamma, eps):
     return value * inv_n, grad
 
 
+def anchor_terms(cls_b, reg_b, anchors, boxes, target, alpha, gamma, eps):
+    """The host statement of the terms of `loss_sampling: anchor` for one sample, in float64: cls_b [4, HW], reg_b [14, HW], anchors
+    [2, 7, HW], boxes [n, >= 7], target int [2 * HW] (label row, -1 negative, -2 ignored; anything else counts as ignored) ->
+    (cls value, reg value without the gain, N = positive anchors, d cls value / d cls_b [4, HW], d reg value / d reg_b [14, HW]).
+    Classification over the anchors j = a * HW + i with target != -2: y = target >= 0, p_t = cls_b[2a + y, i], the focal term and
+    gradient of focal_terms (same clamp), divided by max(1, N).  Regression over the positive anchors: Smooth-L1 of reg_b[7a + c, i]
+    minus the encoded offset of box target(j) against anchor (a, i) (the encoding of LossTotal._reg_term), divided by 7 max(1, N)."""
+    c, r = np.asarray(cls_b, dtype=np.float64), np.asarray(reg_b, dtype=np.float64)
+    an, bx = np.asarray(anchors, dtype=np.float64), np.asarray(boxes, dtype=np.float64).reshape(-1, np.shape(boxes)[-1] if np.ndim(boxes) > 1 else 7)
+    HW = c.shape[1]
+    t = np.asarray(target, dtype=np.int64).reshape(2, HW).copy()
+    t[(t < -2) | (t >= len(bx))] = -2
+    n_pos = int((t >= 0).sum())
+    inv_n = 1.0 / max(1, n_pos)
+    gcls, greg = np.zeros((4, HW)), np.zeros((14, HW))
+    cls_value = reg_value = 0.0
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for a in range(2):
+            y, used = t[a] >= 0, t[a] != -2
+            alpha_t = np.where(y, alpha, 1.0 - alpha)
+            pt = np.where(y, c[2 * a + 1], c[2 * a])
+            q = np.where(pt < eps, eps, pt)
+            lnq = np.log(q)
+            if gamma == 0:
+                fl, g = -alpha_t * lnq, -alpha_t / q
+            else:
+                om = 1.0 - q
+                fl = -alpha_t * om ** gamma * lnq
+                g = alpha_t * gamma * om ** (gamma - 1.0) * lnq - alpha_t * om ** gamma / q
+            cls_value += fl[used].sum()
+            gcls[2 * a + 1] = np.where(y, g, 0.0) * inv_n
+            gcls[2 * a] = np.where(used & ~y, g, 0.0) * inv_n
+            cells = np.flatnonzero(y)
+            if cells.size:
+                A, ref = an[a][:, cells], bx[t[a][cells], :7].T           # [7, m] each
+                diag = np.sqrt(A[3] ** 2 + A[4] ** 2)
+                dyaw = ref[6] - A[6]
+                enc = np.stack(((ref[0] - A[0]) / diag, (ref[1] - A[1]) / diag, (ref[2] - A[2]) / A[5], np.log(ref[3] / A[3]),
+                                np.log(ref[4] / A[4]), np.log(ref[5] / A[5]), np.arctan2(np.sin(dyaw), np.cos(dyaw))))
+                d = r[7 * a:7 * a + 7][:, cells] - enc
+                ad = np.abs(d)
+                reg_value += np.where(ad < 1.0, 0.5 * d * d, ad - 0.5).sum()
+                greg[7 * a:7 * a + 7, cells] = np.where(ad < 1.0, d, np.sign(d)) * (inv_n / 7.0)
+    return cls_value * inv_n, reg_value * (inv_n / 7.0), n_pos, gcls, greg
+
+
 class LossTotal(nn.Module):
     def __init__(self, config):
         super(LossTotal, self).__init__()
@@ -180,10 +231,15 @@ class LossTotal(nn.Module):
         self.regress_type = config["regress_type"]
         self.reduction = config.get("loss_reduction", "last")
         self.sampling = config.get("loss_sampling", "compat")
-        if self.sampling not in ("compat", "device", "hard", "focal"):
-            raise ValueError("loss_sampling must be compat, device, hard or focal (got %r)" % (self.sampling,))
-        self.focal = parse_focal_config(config) if self.sampling == "focal" else None      # (alpha, gamma, eps)
+        if self.sampling not in ("compat", "device", "hard", "focal", "anchor"):
+            raise ValueError("loss_sampling must be compat, device, hard, focal or anchor (got %r)" % (self.sampling,))
+        self.focal = parse_focal_config(config) if self.sampling in ("focal", "anchor") else None      # (alpha, gamma, eps)
+        self.assign_iou = None             # anchor: (assign_pos_iou, assign_neg_iou)
+        if self.sampling == "anchor":
+            from .assign import parse_assign_config
+            self.assign_iou = parse_assign_config(config)
         self.last_terms = None             # focal: [B,3] fp32 = (cls_b, reg_b without the gain, |P_b|) of the last call, unweighted
+                                           # (anchor: the third column is N_b, the positive anchors)
         from .model import parse_deterministic_config
         self.deterministic = parse_deterministic_config(config)      # both device entries then sum in one fixed order (csrc/loss.hip, DET)
         self.seed = int(config.get("loss_seed", 0))
@@ -194,6 +250,8 @@ class LossTotal(nn.Module):
         self.keep_samples = False
         anc = AnchorBoundingBoxFeature(config)()
         self.register_buffer("anchor_set", anc.reshape(2, 7, anc.shape[1], anc.shape[2]), persistent=False)
+        if self.sampling == "anchor" and not bool((torch.isfinite(self.anchor_set[:, [0, 1, 3, 4, 6]]).all() and (self.anchor_set[:, 3:5] > 0).all())):
+            raise ValueError("loss_sampling: anchor needs finite anchors of positive length and width (an IoU against a zero-area anchor is undefined)")
         L, W = config["voxel_length"], config["voxel_width"]
         self._xs = int(L / (config["lidar_x_max"] - config["lidar_x_min"]))
         self._ys = int(W / (config["lidar_y_max"] - config["lidar_y_min"]))
@@ -527,6 +585,74 @@ class LossTotal(nn.Module):
             total += w * (value + gain * lr)
         loss[0] = total
 
+    def _forward_anchor(self, boxes, nbox, cls, reg, anc, B, H, W):
+        """loss_sampling: anchor.  CUDA tensors: dcf_assign_anchors_iou on the staged labels, then dcf_loss_anchor_fwd_bwd on its
+        targets -- five small launches on one stream, no host wait; workspaces, target and counts are allocated once per map shape.
+        CPU tensors: the host statements (assign.anchor_targets, anchor_terms) behind the same autograd function.  Nothing is drawn:
+        calls is not advanced.  With keep_samples, last_samples = (target [B,2,HW], best [B,2,HW] fp64, counts [B,4])."""
+        c = self.config
+        dev = cls.device
+        alpha, gamma, eps = self.focal
+        pos_iou, neg_iou = self.assign_iou
+        gain, red = float(c["regress_loss_gain"]), REDUCTION[self.reduction]
+        ws = getattr(self, "_anchor_ws", None)          # scratch, target, counts and terms: allocated once per map shape
+        key = (B, H, W, boxes.shape[1], dev, bool(self.keep_samples))
+        if dev.type != "cuda":
+            boxes_host = boxes.detach().float()
+            if ws is None or ws[0] != key:
+                ws = self._anchor_ws = (key, torch.zeros((B, 3), dtype=torch.float32))
+            self.last_terms = terms = ws[1]
+
+            def launch(loss, gcls, greg):
+                self._anchor_host(boxes_host, nbox, cls.detach(), reg.detach(), anc, B, H, W, loss, gcls, greg, terms)
+            return _FusedLoss.apply(None, cls, reg, launch)
+        from . import ops
+        boxes, nb = self._stage_labels(boxes, nbox, dev)
+        base, cls, reg = self._head_views(cls, reg, H, W)
+        if ws is None or ws[0] != key:
+            ws = self._anchor_ws = ((key,) + ops.assign_anchors_workspace(B, H, W, boxes.shape[1], dev, best=self.keep_samples)
+                                    + ops.loss_anchor_workspace(B, H, W, dev))
+        _, aws, target, counts, best, lws, terms = ws
+        self.last_terms = terms
+        if self.keep_samples:
+            self.last_samples = (target, best, counts)
+
+        def launch(loss, gcls, greg):
+            ops.assign_anchors_iou(anc, boxes, nb, H, W, pos_iou, neg_iou, target, counts, aws, best=best)
+            ops.loss_anchor(cls, reg, anc, boxes, target, counts, alpha, gamma, eps, gain, red, loss, gcls, greg, terms, lws)
+        return _FusedLoss.apply(base, cls, reg, launch)
+
+    def _anchor_host(self, boxes_host, nbox, cls, reg, anc, B, H, W, loss, gcls, greg, terms):
+        """The host statement of the two anchor entries: fills loss [1], the gradient maps and terms [B,3] in float64 arithmetic.  The
+        device assigns every sample; here only those the reduction counts, unless keep_samples asks for all."""
+        from . import assign
+        alpha, gamma, eps = self.focal
+        pos_iou, neg_iou = self.assign_iou
+        gain = float(self.config["regress_loss_gain"])
+        bh, an = boxes_host.numpy(), anc.detach().float().numpy()
+        HW = H * W
+        terms.zero_()
+        total = 0.0
+        counted = [B - 1] if self.reduction == "last" else list(range(B))
+        w = 1.0 / B if self.reduction == "mean" else 1.0
+        kept = (np.full((B, 2, HW), -1, np.int32), np.zeros((B, 2, HW)), np.zeros((B, 4), np.int32)) if self.keep_samples else None
+        for b in (range(B) if kept is not None else counted):
+            nb = max(min(int(nbox[b]), bh.shape[1]), 0)
+            target, best, counts = assign.anchor_targets(an, bh[b, :nb], pos_iou, neg_iou)
+            if kept is not None:
+                kept[0][b], kept[1][b], kept[2][b] = target.reshape(2, HW), best.reshape(2, HW), counts
+            if b not in counted:
+                continue
+            lc, lr, n_pos, gc, gr = anchor_terms(cls[b].reshape(4, HW).double().numpy(), reg[b].reshape(14, HW).double().numpy(), an,
+                                                 bh[b, :nb], target, alpha, gamma, eps)
+            gcls[b] = torch.from_numpy(gc * w).to(gcls.dtype).reshape(4, H, W)
+            greg[b] = torch.from_numpy(gr * (gain * w)).to(greg.dtype).reshape(14, H, W)
+            terms[b] = torch.tensor([lc, lr, n_pos], dtype=torch.float32)
+            total += w * (lc + gain * lr)
+        if kept is not None:
+            self.last_samples = tuple(torch.from_numpy(v) for v in kept)
+        loss[0] = total
+
     def forward(self, reference_bboxes_batch, num_ref_bbox_batch, predicted_class_feature_batch, predicted_regress_feature_batch):
         cls, reg = predicted_class_feature_batch, predicted_regress_feature_batch
         dev = cls.device
@@ -537,6 +663,8 @@ class LossTotal(nn.Module):
         anc = self._anc_dev
         if self.sampling == "focal":
             return self._forward_focal(reference_bboxes_batch, num_ref_bbox_batch, cls, reg, anc, B, H, W)
+        if self.sampling == "anchor":
+            return self._forward_anchor(reference_bboxes_batch, num_ref_bbox_batch, cls, reg, anc, B, H, W)
         if self.sampling == "device" or (self.sampling == "hard" and dev.type == "cuda"):
             if dev.type != "cuda":
                 raise RuntimeError("loss_sampling: device needs CUDA tensors (the host path is loss_sampling: compat)")

@@ -970,3 +970,44 @@ def loss_focal(cls, reg, anchors, boxes, nbox, grid, span, regress_type, alpha, 
            int(regress_type), float(alpha), float(gamma), float(eps), float(gain), int(reduction), loss, gcls, gcls.stride(0), greg,
            greg.stride(0), terms, ws, H.stream_ptr())
     return loss
+
+
+# ------------------------------------------------------------------ IoU-based anchor assignment (loss_sampling: anchor)
+def assign_anchors_workspace(B, Hh, W, max_box, device, best=False):
+    """(workspace, target int32 [B,2,h*w], counts int32 [B,4], best fp64 [B,2,h*w] or None) of assign_anchors_iou for one map shape;
+    the workspace's contents are free between calls on one stream."""
+    nbytes = H.lib().dcf_assign_anchors_workspace_bytes(B, Hh, W, max_box)
+    if nbytes == 0:
+        raise H.DcfError("assign_anchors_iou: bad map shape / label rows %r" % ((B, Hh, W, max_box),))
+    return (torch.empty(nbytes // 4, dtype=torch.int32, device=device), torch.empty((B, 2, Hh * W), dtype=torch.int32, device=device),
+            torch.empty((B, 4), dtype=torch.int32, device=device), torch.empty((B, 2, Hh * W), dtype=torch.float64, device=device) if best else None)
+
+
+def assign_anchors_iou(anchors, boxes, nbox, Hh, W, pos_iou, neg_iou, target, counts, ws, best=None):
+    """Per-anchor targets by rotated bird's-eye IoU (assign.anchor_targets is the host statement): anchors [2,7,h*w] fp32, boxes
+    [B,max,>=7] fp32 and nbox int32 [B] on the device; target int32 [B,2,h*w] (label row, -1 negative, -2 ignored), counts int32 [B,4] =
+    (positives, ignored, positive through forcing only, void labels) and, if given, best fp64 [B,2,h*w] are written."""
+    B = boxes.shape[0]
+    H.call("dcf_assign_anchors_iou", _chk(anchors, "anchors"), _chk(boxes, "boxes"), _chk(nbox, "nbox"), boxes.shape[1], boxes.shape[2], B, Hh, W,
+           float(pos_iou), float(neg_iou), _chk(target, "target"), None if best is None else _chk(best, "best"), _chk(counts, "counts"), ws,
+           H.stream_ptr())
+    return target, counts
+
+
+def loss_anchor_workspace(B, Hh, W, device):
+    """(workspace, terms [B,3]) of loss_anchor for one map shape; contents free between calls on one stream."""
+    nbytes = H.lib().dcf_loss_anchor_workspace_bytes(B, Hh, W)
+    if nbytes == 0:
+        raise H.DcfError("loss_anchor: bad map shape %r" % ((B, Hh, W),))
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device), torch.zeros((B, 3), dtype=torch.float32, device=device)
+
+
+def loss_anchor(cls, reg, anchors, boxes, target, counts, alpha, gamma, eps, gain, reduction, loss, gcls, greg, terms, ws):
+    """The objective on per-anchor targets and its gradients, one launch and a fold.  cls [B,4,h,w] / reg [B,14,h,w] fp32 views with unit
+    cell stride, anchors [2,7,h*w], boxes [B,max,>=7] fp32, target int32 [B,2,h*w] and counts int32 [B,4] on the device; loss [1], terms
+    [B,3] and every element of gcls / greg of the computed samples are written (no zero fill needed).  reduction: 0 last, 1 sum, 2 mean."""
+    B, _, Hh, W = cls.shape
+    H.call("dcf_loss_anchor_fwd_bwd", cls, cls.stride(0), reg, reg.stride(0), anchors, _chk(boxes, "boxes"), boxes.shape[1], boxes.shape[2],
+           _chk(target, "target"), _chk(counts, "counts"), B, Hh, W, float(alpha), float(gamma), float(eps), float(gain), int(reduction), loss,
+           gcls, gcls.stride(0), greg, greg.stride(0), terms, ws, H.stream_ptr())
+    return loss

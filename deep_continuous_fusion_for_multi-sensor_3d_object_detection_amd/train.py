@@ -774,8 +774,8 @@ class Train(nn.Module):
 
     def loss_terms(self):
         """loss_sampling: focal -- [B,3] fp32 = (classification term, regression term without the gain, positive cells) per sample of
-        the last step, unweighted; zero rows for the samples `loss_reduction: last` leaves out (device tensor, a copy).  None in the
-        other modes."""
+        the last step, unweighted; zero rows for the samples `loss_reduction: last` leaves out (device tensor, a copy).
+        loss_sampling: anchor -- the same, the third column counting positive anchors.  None in the other modes."""
         terms = self.loss_total.last_terms
         return None if terms is None else terms.clone()
 
@@ -1043,7 +1043,8 @@ def main():
         #                                                                    evaluation below and the next save see no open window
         if rank0 and terms_n:
             cls_mean, reg_mean, npos_mean = (terms_sum / terms_n).tolist()
-            print("epoch %d: focal classification %.4f, regression %.4f, positive cells %.1f (batch means)" % (epoch, cls_mean, reg_mean, npos_mean))
+            what = "positive anchors" if training.loss_total.sampling == "anchor" else "positive cells"
+            print("epoch %d: focal classification %.4f, regression %.4f, %s %.1f (batch means)" % (epoch, cls_mean, reg_mean, what, npos_mean))
         _eval_barrier()
         if rank0:                                                          # train.py:105-122
             mean, cum, npos, nt, tp = evaluate(training, tester, test_dataset, test_loader, max_batches=int(config.get("eval_batches_epoch", 12)))   # `batch_ndx > 10`

@@ -677,6 +677,38 @@ int dcf_loss_focal_fwd_bwd_det(const float *cls, int64_t cls_bstride, const floa
                                float gamma, float eps, float reg_gain, int reduction, float *loss, float *gcls, int64_t gcls_bstride,
                                float *greg, int64_t greg_bstride, float *terms, void *workspace, dcf_stream_t stream);
 
+/* (version 202 still: added without a new minor) IoU-based anchor assignment (`loss_sampling: anchor`; assign.py
+ * and loss.anchor_terms are the host statements).  Anchor index j = a*H*W + i for anchor a in {0, 1} and cell i.
+ * dcf_assign_anchors_iou: I(j, k) = the bird's-eye IoU of anchor j's (x, y) rectangle clipped by label k's, in fp64 on the fp32 inputs
+ *   (the geometry of dcf_eval_nms mode 2); a label row k < min(nbox, max_box) with a non-finite x, y, l, w or yaw, or l <= 0 or w <= 0, is
+ *   VOID: I = 0 everywhere.  best(j) = max_k I(j, k) (0 without labels), arg(j) = the lowest k attaining it; forced(k) = the j of highest
+ *   I(j, k) provided that is > 0, ties to the lowest j.  target(j) = the lowest k with forced(k) == j; else arg(j) if best(j) >= pos_iou;
+ *   else -1 (negative) if best(j) < neg_iou; else -2 (ignored).  A pair whose centres are further apart than the two half-diagonals
+ *   together skips the clip (its value there is exactly 0).  Anchors must have l, w > 0.
+ *   target int32 [B][2][H*W], best fp64 [B][2][H*W] or NULL, counts int32 [B][4] = (N_b = positive anchors, ignored anchors, anchors
+ *   positive through forcing only, void labels).  All B samples are assigned.  0 < neg_iou <= pos_iou <= 1, max_box in 1..64,
+ *   box_stride >= 7, H*W < 2^30.  workspace: dcf_assign_anchors_workspace_bytes(B, H, W, max_box) bytes, 8-byte aligned, contents free on
+ *   entry; calls that share it must be ordered on one stream.  Integer and fp64 work in a fixed order: no atomics.
+ * dcf_loss_anchor_fwd_bwd: the terms on such targets.  Classification over every j with target != -2: y = target >= 0,
+ *   p_t = cls[2a+y][i], alpha_t = y ? alpha : 1 - alpha, FL and its gradient those of dcf_loss_focal_fwd_bwd (same clamp: a NaN score stays
+ *   NaN), cls_b = sum FL / max(1, N_b), N_b = counts[b][0]; the other channel of the pair, and both channels of an ignored anchor, get 0.
+ *   Regression over the positive j, box k = target(j), components c = 0..6: d = reg[7a+c][i] - (the encoded offset of box k against
+ *   anchor (a, i), as in the other entries), reg_b = sum SmoothL1(d) / (7 max(1, N_b)).  total_b = cls_b + reg_gain * reg_b; *loss is
+ *   stored: partial values added in a fixed order in double, rounded once.  reduction 0 computes the last sample only.
+ *   EVERY element of the 4 gcls and 14 greg channels of a computed sample is stored: no atomics, no zero fill needed, one entry for
+ *   deterministic and plain runs.  A target outside [-2, max_box) counts as ignored.  terms fp32 [B][3] = (cls_b, reg_b without the
+ *   gain, N_b), zero rows for samples that reduction 0 leaves out.  alpha, gamma, eps as for the focal entry.
+ *   workspace: dcf_loss_anchor_workspace_bytes(B, H, W) bytes, 4-byte aligned, contents free on entry. */
+size_t dcf_assign_anchors_workspace_bytes(int B, int H, int W, int max_box);
+int dcf_assign_anchors_iou(const float *anchors, const float *boxes, const int32_t *nbox_dev, int max_box, int box_stride, int B, int H,
+                           int W, double pos_iou, double neg_iou, int32_t *target, double *best, int32_t *counts, void *workspace,
+                           dcf_stream_t stream);
+size_t dcf_loss_anchor_workspace_bytes(int B, int H, int W);
+int dcf_loss_anchor_fwd_bwd(const float *cls, int64_t cls_bstride, const float *reg, int64_t reg_bstride, const float *anchors,
+                            const float *boxes, int max_box, int box_stride, const int32_t *target, const int32_t *counts, int B, int H,
+                            int W, float alpha, float gamma, float eps, float reg_gain, int reduction, float *loss, float *gcls,
+                            int64_t gcls_bstride, float *greg, int64_t greg_bstride, float *terms, void *workspace, dcf_stream_t stream);
+
 /* ------------------------------------------------- evaluation post-processing
  * What /root/reference/test.py:88-206 does on the host, box by box.
  * dcf_eval_score_filter: test.py:88-108.  pred [B][32][h][w] fp32 (the model output: scores in channels 2a+1, decoded boxes in
