@@ -521,6 +521,110 @@ def augment_image_batch(img_u8, params, out=None):
     return out
 
 
+PASTE_STAGE_BYTES = 8192       # the staging buffers of dcf_paste_*_batch: at least the larger table (5440 bytes for 8 frames)
+PASTE_VALUE_MAX = 4            # up to this many frames per call the tables travel in the kernel argument: no staging
+_paste_rings = {}
+
+
+def _paste_stage(dev):
+    """(pinned host buffer, device buffer) for one paste launch of 5 .. 8 frames on the current stream: a ring of four pairs per device (the way of
+    LossTotal._stage) -- the pair being refilled was last used four launches ago, so the wait for its event does not block.  The
+    event is recorded behind the launch (paste_stage_done), so neither the copy nor the kernel can still read the pair."""
+    ring = _paste_rings.get(dev)
+    if ring is None:
+        ring = _paste_rings[dev] = {"slot": 0, "sets": [[torch.empty(PASTE_STAGE_BYTES, dtype=torch.uint8).pin_memory(),
+                                                          torch.empty(PASTE_STAGE_BYTES, dtype=torch.uint8, device=dev), None] for _ in range(4)]}
+    st = ring["sets"][ring["slot"]]
+    ring["slot"] = (ring["slot"] + 1) % len(ring["sets"])
+    if st[2] is not None:
+        st[2].synchronize()
+    return st
+
+
+def _paste_stage_done(st):
+    st[2] = torch.cuda.Event()
+    st[2].record()
+
+
+def paste_points_batch(pts_list, plans, bank_points, out_list):
+    """Train-time object pasting, the points (paste.py): pts_list = B device tensors [n_b,3] fp32 (views at any
+    point offset of a larger buffer included), plans = B paste.draw results, bank_points = the bank's `points` on the device
+    [P,3] fp32, out_list = B contiguous fp32 device tensors [rows_b,3] with rows_b >= n_b + a_b, overlapping no input.  Bit for bit
+    paste.paste_points per frame; rows past n_b + a_b are not written.  One launch per 8 frames; its table travels in the kernel
+    argument (up to 4 frames) or in one asynchronous copy from a pinned ring on the current stream (5 .. 8).  Returns the B views
+    out_list[b][:n_b + a_b]."""
+    B = len(pts_list)
+    if len(plans) != B or len(out_list) != B:
+        raise H.DcfError("paste_points_batch: %d frames, %d plans, %d outputs" % (B, len(plans), len(out_list)))
+    for t in list(pts_list) + list(out_list) + [bank_points]:
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == 3):
+            raise H.DcfError("paste_points_batch: frames, outputs and the bank must be contiguous fp32 CUDA tensors [n,3]")
+    res = []
+    for b0 in range(0, B, 8):
+        sl = slice(b0, min(b0 + 8, B))
+        k = sl.stop - sl.start
+        rec, app = np.zeros((k, 16, 8), dtype=np.float32), np.zeros((k, 16, 2), dtype=np.int64)
+        ms = (ctypes.c_int * k)()
+        for i, p in enumerate(plans[sl]):
+            m = len(p["records"])
+            if m > 16 or len(p["append"]) != m:
+                raise H.DcfError("paste_points_batch: a plan holds at most 16 records, one append entry each")
+            ms[i] = m
+            rec[i, :m], app[i, :m] = p["records"], p["append"]
+        ptrs = (ctypes.c_void_p * k)(*[p.data_ptr() if p.shape[0] else None for p in pts_list[sl]])
+        outs = (ctypes.c_void_p * k)(*[o.data_ptr() if o.shape[0] else None for o in out_list[sl]])
+        ns = (ctypes.c_int * k)(*[int(p.shape[0]) for p in pts_list[sl]])
+        caps = (ctypes.c_int * k)(*[int(o.shape[0]) for o in out_list[sl]])
+        st = _paste_stage(bank_points.device) if k > PASTE_VALUE_MAX else (None, None)
+        H.call("dcf_paste_points_batch", ctypes.addressof(ptrs), ctypes.addressof(ns), k, ctypes.addressof(ms), rec, app,
+               bank_points if bank_points.shape[0] else None, int(bank_points.shape[0]), ctypes.addressof(outs), ctypes.addressof(caps),
+               st[0], st[1], PASTE_STAGE_BYTES, H.stream_ptr())
+        if k > PASTE_VALUE_MAX:
+            _paste_stage_done(st)
+        for i in range(k):
+            res.append(out_list[b0 + i][:ns[i] + int(app[i, :ms[i], 1].sum())])
+    return res
+
+
+def paste_patches_batch(img_u8, plans, bank_patch, out):
+    """Train-time object pasting, the image patches (paste.py): img_u8 = a contiguous uint8 device tensor
+    [B,3,H,W] (a view at any byte offset of a larger buffer included), plans = B paste.draw results, bank_patch = the bank's `patch`
+    bytes on the device, out = a contiguous uint8 [B,3,H,W] tensor that does not overlap the input (the batch's image is a view of
+    the loader's staging set) -- ValueError.  Byte for byte paste.paste_image per frame.  One launch per 8 frames.  Returns out."""
+    for name, t in (("img_u8", img_u8), ("out", out), ("bank_patch", bank_patch)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+            raise H.DcfError("paste_patches_batch: %s must be a contiguous uint8 CUDA tensor" % name)
+    if img_u8.dim() != 4 or img_u8.shape[1] != 3 or img_u8.numel() == 0:
+        raise H.DcfError("paste_patches_batch: image must be [B,3,H,W] (got %s)" % (tuple(img_u8.shape),))
+    B, _, Hh, Ww = (int(v) for v in img_u8.shape)
+    if len(plans) != B:
+        raise H.DcfError("paste_patches_batch: %d frames, %d plans" % (B, len(plans)))
+    for p in plans:                                  # drawn for another image size: the clipping would be another
+        if tuple(p.get("image_hw", (Hh, Ww))) != (Hh, Ww):
+            raise ValueError("paste_patches_batch: a plan of %s images for %d x %d ones" % (tuple(p["image_hw"]), Hh, Ww))
+    if tuple(out.shape) != tuple(img_u8.shape) or out.device != img_u8.device:
+        raise H.DcfError("paste_patches_batch: out must be %s on the image's device" % (tuple(img_u8.shape),))
+    nbytes = img_u8.numel()
+    if img_u8.data_ptr() < out.data_ptr() + nbytes and out.data_ptr() < img_u8.data_ptr() + nbytes:
+        raise ValueError("paste_patches_batch: out overlaps the input")
+    for b0 in range(0, B, 8):
+        k = min(b0 + 8, B) - b0
+        rec = np.zeros((k, 16, 9), dtype=np.int64)
+        ms = (ctypes.c_int * k)()
+        for i, p in enumerate(plans[b0:b0 + k]):
+            m = len(p["patches"])
+            if m > 16:
+                raise H.DcfError("paste_patches_batch: a plan holds at most 16 patch records")
+            ms[i] = m
+            rec[i, :m] = p["patches"]
+        st = _paste_stage(img_u8.device) if k > PASTE_VALUE_MAX else (None, None)
+        H.call("dcf_paste_patches_batch", img_u8[b0:b0 + k], k, Hh, Ww, ctypes.addressof(ms), rec, bank_patch if bank_patch.numel() else None,
+               int(bank_patch.numel()), out[b0:b0 + k], st[0], st[1], PASTE_STAGE_BYTES, H.stream_ptr())
+        if k > PASTE_VALUE_MAX:
+            _paste_stage_done(st)
+    return out
+
+
 def knn_bev(xyz, cnt, K, h, w, stride, aff, rmax=None, ws=None, out=None):
     """out: optional int32 [K,h,w] tensor to write into (e.g. a frame's slice of a batch tensor)."""
     n_max = xyz.shape[0]

@@ -219,6 +219,55 @@ def parse_image_augment_config(config):
     return out if enabled else None
 
 
+def parse_paste_config(config):
+    """The `augment_paste` block (paste.py), validated like the other two: None = off (no block, or
+    enabled: false), else {"seed", "bank" (path of the .npz), "target_objects", "max_candidates" (1..16), "margin" (metres, >= 0),
+    "paste_image"}.  Bad values raise ValueError whether the block is enabled or not; an enabled block needs a bank."""
+    from . import paste as PST
+    blk = config.get("augment_paste", None)
+    if blk is None:
+        return None
+    if not isinstance(blk, dict):
+        raise ValueError("augment_paste must be a mapping (got %r)" % (blk,))
+    unknown = sorted(set(blk) - set(PST.KEYS))
+    if unknown:
+        raise ValueError("augment_paste: unknown keys %s (known: %s)" % (unknown, list(PST.KEYS)))
+    enabled, with_image = blk.get("enabled", False), blk.get("paste_image", True)
+    for key, v in (("enabled", enabled), ("paste_image", with_image)):
+        if not isinstance(v, bool):
+            raise ValueError("augment_paste.%s must be true or false (got %r)" % (key, v))
+    seed = blk.get("seed", 0)
+    if isinstance(seed, bool) or not isinstance(seed, int):
+        raise ValueError("augment_paste.seed must be an integer (got %r)" % (seed,))
+    bank = blk.get("bank", None)
+    if bank is not None and not isinstance(bank, str):
+        raise ValueError("augment_paste.bank must be the path of an object bank (got %r)" % (bank,))
+    out = {"seed": int(seed), "bank": bank, "target_objects": blk.get("target_objects", 15), "max_candidates": blk.get("max_candidates", 16),
+           "margin": blk.get("margin", 0.0), "paste_image": with_image}
+    PST.check_config(out)
+    out["margin"] = float(out["margin"])
+    if not enabled:
+        return None
+    if not bank:
+        raise ValueError("augment_paste.bank: an enabled block needs the path of an object bank (python -m <package>.objbank --out PATH)")
+    return out
+
+
+def draw_paste_plans(cfg, bank, rank, call, boxes, nums, n_points, crts, config):
+    """The per-frame plans of one step (paste.draw) and the labels with the pasted rows behind the frame's own, all on the host:
+    (plans, boxes' float32 [B, max_num_bbox, 9], nums' [B]).  cfg None (block absent or disabled): empty plans, the labels as
+    they came."""
+    from . import paste as PST
+    src = np.asarray(boxes, dtype=np.float32)
+    cnt = [int(v) for v in np.asarray(nums).reshape(-1)]
+    hw = (int(config["image_height"]), int(config["image_width"])) if bank is None else bank["image_hw"]
+    if cfg is None:
+        return [PST.empty_plan(n_points[b], hw) for b in range(len(cnt))], src, cnt
+    plans = [PST.draw(cfg, cfg["seed"], rank, call, b, bank, src[b], cnt[b], n_points[b], crts[b], config) for b in range(len(cnt))]
+    moved = [PST.append_labels(src[b], cnt[b], plans[b]) for b in range(len(cnt))]
+    return plans, np.stack([m[0] for m in moved], 0), [m[1] for m in moved]
+
+
 class FlatAdam(object):
     """Adam(lr, betas=(beta1, 0.999), eps=1e-8) of train.py:28 on the flat parameter arena.
     guard (parse_guard_config): the guarded step of csrc/amp.hip -- loss scale, non-finite skip and clipping decided on the
@@ -407,6 +456,21 @@ class Train(nn.Module):
         # written and read on the compute stream
         self.image_augment = parse_image_augment_config(config)
         self._aug_image = None
+        # train-time object pasting (paste.py, objbank.py; None = off, the default: no bank, no buffer, no launch).  The third block
+        # on the same (seed, rank, aug_calls, frame); the bank's points and patch bytes are uploaded here, once; last_paste = the
+        # accepted bank rows per frame of the last step (host lists, for logs)
+        self.paste = parse_paste_config(config)
+        self._paste_bank, self._paste_dev, self._paste_image_buf = None, None, None
+        self.last_paste = []
+        if self.paste is not None:
+            from . import objbank, paste as PST
+            try:
+                self._paste_bank = objbank.load(self.paste["bank"])
+            except OSError as e:
+                raise ValueError("augment_paste.bank: cannot read %r (%s)" % (self.paste["bank"], e))
+            PST.check_bank(self._paste_bank, (config["image_height"], config["image_width"]) if self.paste["paste_image"] else None)
+            dev = self.model.flat_params.device
+            self._paste_dev = (torch.from_numpy(self._paste_bank["points"]).to(dev), torch.from_numpy(self._paste_bank["patch"]).to(dev))
         # the accumulator of gradient accumulation: allocated only when a window holds more than one micro-step
         self.accum_buf = torch.empty_like(self.model.flat_grads.detach()) if self.accum is not None else None
         self._accum_index = 0
@@ -462,7 +526,7 @@ class Train(nn.Module):
             self._geo_sets[key] = st
         return st
 
-    def geometry_async(self, frame_geometry, points_list, crts=None, wait_event=None, augment=None, image_augment=None):
+    def geometry_async(self, frame_geometry, points_list, crts=None, wait_event=None, augment=None, image_augment=None, paste=None):
         """Per-frame geometry (voxelise, project, KNN of the fusion sites) on a side HIP stream, so that these
         small latency-bound kernels overlap the camera stream's convolutions on the compute stream.
         Returns (x_lidar [B,Cz,L,W], geom) where geom carries the events the engine waits on.
@@ -474,6 +538,9 @@ class Train(nn.Module):
         image_augment: optional per-frame parameters (augment_image.draw) of an image that was zoomed / shifted / flipped: the
         projection matrices (after the BEV composition) move every point's pixel along (augment_image.compose_crt_image); points
         that now project outside the image fail the projection kernel's limit test as it is.
+        paste: optional per-frame plans (paste.draw): the side stream FIRST writes the pasted frames (scene points inside a pasted
+        box as +inf rows, the bank's points appended) into a persistent buffer of the geometry set; `augment` then reads that
+        buffer -- its point-drop hash simply runs over the longer frame.
         The returned tensors live in one of two persistent buffer sets (config static_geometry, default on): they stay
         valid until the second-next call."""
         main = torch.cuda.current_stream()
@@ -502,6 +569,20 @@ class Train(nn.Module):
             st["used"] = True
         with torch.cuda.stream(self._side):
             pcs, uvs, cnts = [], [], []
+            if paste is not None:
+                if len(paste) != Bn:
+                    raise ValueError("paste: %d plans for %d frames" % (len(paste), Bn))
+                if self._paste_dev is None:
+                    raise ValueError("paste: the trainer was built without an object bank (augment_paste)")
+                src = [frame_geometry._pts(p) for p in points_list]
+                rows = [int(p.shape[0]) + int(q["append"][:, 1].sum()) for p, q in zip(src, paste)]
+                if st is not None and max(rows) <= mp:  # fixed addresses, as the augmented points below
+                    if "paste" not in st:
+                        st["paste"] = torch.empty((Bn, mp, 3), dtype=torch.float32, device=src[0].device)
+                    dst = [st["paste"][b] for b in range(Bn)]
+                else:
+                    dst = [torch.empty((r, 3), dtype=torch.float32, device=src[0].device) for r in rows]
+                points_list = ops.paste_points_batch(src, list(paste), self._paste_dev[0], dst)
             if augment is not None:
                 from . import augment as AUG
                 if len(augment) != Bn:
@@ -716,6 +797,8 @@ class Train(nn.Module):
         """One train step from a FrameLoader batch (raw points + image in HBM): geometry on the side stream, then one_step."""
         batch.wait()
         boxes, nums, params = batch["bboxes"], batch["num_bboxes"], None
+        if self.paste is not None:
+            return self._one_step_raw_paste(frame_geometry, batch)
         if self.image_augment is None:             # the step as it is without the image block
             if self.augment is not None:
                 params, boxes, nums = self._draw_augment(frame_geometry, boxes, nums)
@@ -731,6 +814,47 @@ class Train(nn.Module):
         x_lidar, geom = self.geometry_async(frame_geometry, batch["points"], crts=batch.get("crt"), wait_event=batch.event, augment=params,
                                             image_augment=iparams)
         self.one_step(x_lidar, image, boxes, nums, geom=geom)
+
+    def _one_step_raw_paste(self, frame_geometry, batch):
+        """one_step_raw with the paste block on: paste, then `augment`, then `augment_image`, every block drawn
+        at the step's one call count, which ticks once.  Everything is pasted in the un-augmented frame: the labels get the pasted
+        rows before augment.transform_boxes moves them, the side stream writes the pasted points in front of the BEV transform, and
+        the patches are painted (compute stream, one persistent buffer) in front of the image transform."""
+        call = self.aug_calls
+        boxes, nums, params, iparams = batch["bboxes"], batch["num_bboxes"], None, None
+        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+        points, crts = batch["points"], batch.get("crt")
+        own = [frame_geometry.crt if (crts is None or crts[b] is None) else crts[b] for b in range(len(points))]
+        plans, new_boxes, new_nums = draw_paste_plans(self.paste, self._paste_bank, rank, call, boxes.detach().cpu().numpy(), torch.as_tensor(nums).numpy(),
+                                                      [int(p.shape[0]) for p in points], own, frame_geometry.config)
+        self.last_paste = [list(p["rows"]) for p in plans]
+        boxes = torch.from_numpy(new_boxes).to(boxes.dtype)
+        nums = torch.tensor(new_nums, dtype=torch.as_tensor(nums).dtype)
+        if self.augment is not None:               # (draws at aug_calls == call and counts it)
+            params, boxes, nums = self._draw_augment(frame_geometry, boxes, nums)
+        self.aug_calls = call + 1
+        image = batch["image"]
+        if self.paste["paste_image"]:
+            image = self._paste_image(image, plans)
+        if self.image_augment is not None:
+            image, iparams = self._augment_image(image, call)
+        x_lidar, geom = self.geometry_async(frame_geometry, points, crts=crts, wait_event=batch.event, augment=params, image_augment=iparams,
+                                            paste=plans)
+        self.one_step(x_lidar, image, boxes, nums, geom=geom)
+
+    def _paste_image(self, image, plans):
+        """The batch's uint8 [B,3,H,W] image with this step's patches painted in: one launch on the compute stream -- the stream of
+        its consumer (`_augment_image` or the model), so no events -- into the trainer's one persistent buffer (allocated on first
+        use, re-made when the shape changes); the batch's own image, a view of the loader's staging set, is not written."""
+        if image.dtype != torch.uint8 or image.dim() != 4 or not image.is_cuda:
+            raise ValueError("augment_paste needs the batch's image as a uint8 [B,3,H,W] device tensor (got %s %s)" % (image.dtype, tuple(image.shape)))
+        if tuple(int(v) for v in image.shape[2:]) != tuple(int(v) for v in self._paste_bank["image_hw"]):
+            raise ValueError("augment_paste: the bank holds patches of %s images, the batch's are %s"
+                             % (tuple(int(v) for v in self._paste_bank["image_hw"]), tuple(image.shape[2:])))
+        buf = self._paste_image_buf
+        if buf is None or buf.shape != image.shape or buf.device != image.device:
+            buf = self._paste_image_buf = torch.empty(tuple(image.shape), dtype=torch.uint8, device=image.device)
+        return ops.paste_patches_batch(image.contiguous(), plans, self._paste_dev[1], buf)
 
     def _augment_image(self, image, call):
         """This step's per-frame image parameters (augment_image.draw at `call`) and the augmented uint8 [B,3,H,W] image: one launch
@@ -1020,8 +1144,12 @@ def main():
                 torch.save(training.ema_state_dict(), "./saved_model/" + config["saved_model_name"] + "_ema")
             print("epoch %d: learning rate %.6g" % (epoch, training.learning_rate()))
         terms_sum, terms_n = None, 0                                       # focal: the epoch's mean terms, added up on the device
+        pasted, pasted_frames = 0, 0                                       # augment_paste: accepted objects / frames of the epoch
         for batch_ndx, batch in enumerate(loader):
             training.one_step_raw(dataset.geometry, batch)
+            if training.paste is not None:
+                pasted += sum(len(rows) for rows in training.last_paste)
+                pasted_frames += len(training.last_paste)
             terms = training.loss_terms()
             if terms is not None:                                          # (the batch mean is over the samples the reduction counts)
                 counted = terms[-1:] if training.loss_total.reduction == "last" else terms
@@ -1041,6 +1169,8 @@ def main():
                 _eval_barrier()
         training.finish_window()                                           # a short last window steps with what it has: the
         #                                                                    evaluation below and the next save see no open window
+        if rank0 and pasted_frames:
+            print("epoch %d: %.2f pasted objects per frame (%d frames)" % (epoch, pasted / pasted_frames, pasted_frames))
         if rank0 and terms_n:
             cls_mean, reg_mean, npos_mean = (terms_sum / terms_n).tolist()
             what = "positive anchors" if training.loss_total.sampling == "anchor" else "positive cells"

@@ -120,6 +120,33 @@ int dcf_augment_points_batch(const float *const *pts, const int *n, int B, const
  *   out = clamp(rint(t), 0, 255), round half to even; a tap outside the image contributes 0. */
 int dcf_augment_image_batch(const uint8_t *img, int B, int H, int W, const float *q, uint8_t *out, dcf_stream_t stream);
 
+/* Train-time object pasting, the points (host statement: paste.py) for the B (<= 8) frames of a batch in one
+ * launch.  HOST arrays: pts / out B device pointers (4-byte aligned), n B row counts, m B record counts (<= 16), rec float[B][16][8] =
+ * {cx, cy, cz, cos yaw, sin yaw, l/2 + margin, w/2 + margin, h/2 + margin} (rounded once from float64), app int64[B][16][2] =
+ * (first bank row, rows) of the pasted objects, out_rows B output capacities in rows.  bank: device fp32 [bank_rows][3].
+ * Frame b, a_b = the sum of its objects' rows: output row i < n_b is the source row bit for bit, or (+inf, +inf, +inf) when,
+ * for any record, every operation rounded to fp32 and nothing contracted,
+ *   dx = x - cx   dy = y - cy   lx = dx c + dy s   ly = dy c - dx s   |lx| <= hl && |ly| <= hw && |z - cz| <= hh
+ * (NaN / infinite coordinates compare false); row n_b + prefix_j + i is bank row start_j + i; nothing is written beyond row
+ * n_b + a_b (<= out_rows[b], refused otherwise).  An output overlaps no input, no other output and not the bank (refused).
+ * The per-frame tables: up to 4 frames they travel in the kernel argument and the staging pointers may be NULL.  5 .. 8 frames
+ * need stage_host / stage_dev: stage_bytes >= 8192 of PINNED host memory and of device memory, 8-byte aligned: the call packs its
+ * table into stage_host and enqueues ONE copy to stage_dev in front of the launch, on `stream`; both stay untouched until the
+ * stream has passed the launch (the caller keeps a ring).  The host never waits. */
+int dcf_paste_points_batch(const float *const *pts, const int *n, int B, const int *m, const float *rec, const int64_t *app,
+                           const float *bank, int64_t bank_rows, float *const *out, const int *out_rows, void *stage_host,
+                           void *stage_dev, size_t stage_bytes, dcf_stream_t stream);
+
+/* Train-time object pasting, the image patches, for the B (<= 8) frames of a batch in one launch.  img / out: device uint8
+ * [B][3][H][W], contiguous, ANY byte alignment, 3 H W <= 2^30, not overlapping (refused).  HOST arrays: m B record counts (<= 16),
+ * rec int64[B][16][9] = {x0, y0, w, h, sx, sy, pw, ph, start}: the destination rectangle inside the image, the offset of its first
+ * pixel inside the patch, the patch's width and height, and the first byte of the patch [3][ph][pw] in bank (device uint8
+ * [bank_bytes]); every index is checked on the host.  Output byte (c, y, x) = bank[start + (c ph + (y - y0 + sy)) pw + (x - x0 + sx)]
+ * of the LAST listed record whose rectangle contains (x, y), the input byte where none does: a function of the output pixel
+ * alone, no atomics, no dependence on launch order.  stage_host / stage_dev as in dcf_paste_points_batch. */
+int dcf_paste_patches_batch(const uint8_t *img, int B, int H, int W, const int *m, const int64_t *rec, const uint8_t *bank,
+                            int64_t bank_bytes, uint8_t *out, void *stage_host, void *stage_dev, size_t stage_bytes, dcf_stream_t stream);
+
 /* BEV K-nearest-neighbour (reference: model.py:199-203 TODO; spec SURVEY.md App. D).
  * xyz [n_max][3], first *count_dev rows valid.  idx_out int32 [K][h][w], -1 padding.
  * rmax2 < 0 = unbounded.  K <= 8.  ws: dcf_knn_workspace_bytes(n_max,h,w). */
