@@ -1006,7 +1006,7 @@ __global__ void __launch_bounds__(256) k_relu_mask_rowscale_bwd(const T *__restr
 
 // ------------------------------------------------------------------------------------
 // Train-mode BatchNorm2d (model.py:20,24,29 when the module is in .train(): batch statistics).
-//   stats : per-channel sum / sum-of-squares partials per workgroup, finalised in double
+//   stats : per-channel sum / sum-of-squares partials (about a pivot, see below) per workgroup, finalised in double
 //           (mean, biased var -> invstd; running stats updated with momentum, unbiased var)
 //   apply : y = act(gamma*(x-mean)*invstd + beta + res)
 //   bwd   : dbeta = sum g, dgamma = sum g*xhat, dx = gamma*invstd*(g - dbeta/M - xhat*dgamma/M)
@@ -1016,6 +1016,18 @@ __global__ void __launch_bounds__(256) k_relu_mask_rowscale_bwd(const T *__restr
 // without atomics: every thread parks its 2 V sums in LDS and each of the 2 C outputs is summed, in thread order, by one thread
 // (round 5: LDS atomics from 256 threads onto C / V channel groups serialised 8- to 64-fold -- ~11 us per launch whatever the
 // tensor's size, 1.3 ms of the 8.7 ms train-mode step over its 62 + 62 launches; the sums are now bitwise reproducible too).
+//
+// The forward statistics are sums about a per-channel PIVOT p, the channel's value at the first pixel: s = sum (x - p),
+// q = sum (x - p)^2, mean = p + s / n, var = q / n - (s / n)^2.  The fp32 partials lose a fraction of the energy they carry, and
+// the raw sums sum x, sum x^2 carry n mean^2 on top of the centred energy: summed raw, an fp32 channel with |mean| / std = 4096
+// came out with invstd 0.708 for 0.251, a constant channel x = 3.3 with invstd 284 for 316 and a single pixel with 309 for 316
+// (tests/test_gpu_bn_edges.py); the double finalisation cannot bring that back.  About the pivot the energy is the centred one
+// plus n (p - mean)^2 -- a few times it for a pivot drawn from the channel, whatever |mean| / std (an outlier AS the first pixel
+// is the case this does not cover) -- and a constant channel has s = q = 0 exactly.  A pivot that is not finite is replaced by
+// 0 (inf - inf would turn the channel's mean from inf into NaN).  Cost: one more vector load per thread, the same line for a
+// whole channel group.
+__device__ __forceinline__ float bn_pivot(float v) { return fabsf(v) <= 3.402823466e38f ? v : 0.f; }
+
 template <typename T, bool BWD, int V>
 __global__ void __launch_bounds__(256) k_bn_partial(const T *x, const T *g, const float *mean, const float *invstd, float *partial,
                                                     int64_t nvec, int cgroups, int64_t stride)
@@ -1035,6 +1047,10 @@ __global__ void __launch_bounds__(256) k_bn_partial(const T *x, const T *g, cons
         if (BWD) {
 #pragma unroll
             for (int k = 0; k < V; ++k) { mu[k] = mean[cg * V + k]; is[k] = invstd[cg * V + k]; }
+        } else {
+            ldv<V>(x + (int64_t)cg * V, mu);       // the pivots of this thread's channels: pixel 0
+#pragma unroll
+            for (int k = 0; k < V; ++k) mu[k] = bn_pivot(mu[k]);
         }
         auto add = [&](const float (&xx)[V], const float (&gg)[V]) __attribute__((always_inline)) {
             if (BWD) {
@@ -1042,7 +1058,7 @@ __global__ void __launch_bounds__(256) k_bn_partial(const T *x, const T *g, cons
                 for (int k = 0; k < V; ++k) { a[k] += gg[k]; b[k] += gg[k] * ((xx[k] - mu[k]) * is[k]); }
             } else {
 #pragma unroll
-                for (int k = 0; k < V; ++k) { a[k] += xx[k]; b[k] += xx[k] * xx[k]; }
+                for (int k = 0; k < V; ++k) { const float d = xx[k] - mu[k]; a[k] += d; b[k] += d * d; }
             }
         };
         int64_t e = t;
@@ -1083,18 +1099,22 @@ __device__ __forceinline__ double wave_sum_d(double v)
     return v;
 }
 
-// one wave per channel: lanes stride over the workgroup partials (fixed mapping => reproducible), double sums
-__global__ void __launch_bounds__(64) k_bn_stats_final(const float *partial, int nblk, int C, double count, float eps, float momentum,
+// one wave per channel: lanes stride over the workgroup partials (fixed mapping => reproducible), double sums; x gives the
+// channel's pivot (pixel 0), about which k_bn_partial summed
+template <typename T>
+__global__ void __launch_bounds__(64) k_bn_stats_final(const T *x, const float *partial, int nblk, int C, double count, float eps, float momentum,
                                                        float *mean, float *invstd, float *running_mean, float *running_var)
 {
     const int c = blockIdx.x;
+    const float p = bn_pivot(DT<T>::ld(x + c));    // loaded with the partials: behind them (lane 0, after the sums) it cost 0.05 ms of the 7.9 ms train step
     double s = 0.0, q = 0.0;
     for (int b = threadIdx.x; b < nblk; b += 64) { s += partial[(int64_t)b * 2 * C + c]; q += partial[(int64_t)b * 2 * C + C + c]; }
     s = wave_sum_d(s);
     q = wave_sum_d(q);
     if (threadIdx.x != 0) return;
-    const double m = s / count;
-    double var = q / count - m * m;
+    const double off = s / count;                  // mean - pivot
+    const double m = (double)p + off;
+    double var = q / count - off * off;
     if (var < 0.0) var = 0.0;
     mean[c] = (float)m;
     invstd[c] = (float)(1.0 / sqrt(var + (double)eps));
@@ -1133,8 +1153,9 @@ __global__ void __launch_bounds__(256) k_bn_apply_fwd(const T *x, const float *m
         for (int k = 0; k < V; ++k) o[k] += r[k];
     }
     if (relu) {
+        // a NaN stays a NaN, as in torch.relu (fmaxf would turn a channel whose statistics are not finite into zeros)
 #pragma unroll
-        for (int k = 0; k < V; ++k) o[k] = fmaxf(o[k], 0.f);
+        for (int k = 0; k < V; ++k) o[k] = (o[k] > 0.f || o[k] != o[k]) ? o[k] : 0.f;
     }
     stv<V>(y + e * V, o);
 }
@@ -1448,8 +1469,11 @@ extern "C" int dcf_relu_mask_rowscale_bwd(int dtype, const void *gy, const void 
 static inline int bn_blocks(int64_t nvec, int cg, int64_t *stride)
 {
     // <= 512 workgroups of partials; four vectors per thread where the tensor is small (a quarter of the partial rows for the
-    // finalisation kernel to walk)
-    int64_t want = std::min<int64_t>((nvec + 3) / 4, 128 * 1024);
+    // finalisation kernel to walk).  BN_KTHREADS (units of 1024 threads, default and upper limit 128: the workspace holds 512
+    // workgroups' partials) lowers the cap so that a test tensor of a few thousand vectors walks more than one trip.
+    static DcfOpt env_o("BN_KTHREADS"); const char *env = env_o.str();
+    const int kthreads = env ? std::min(std::max(atoi(env), 1), 128) : 128;
+    int64_t want = std::min<int64_t>((nvec + 3) / 4, kthreads * 1024ll);
     if (want < cg) want = cg;
     *stride = want / cg * cg;
     return cdiv(*stride, 256);
@@ -1473,7 +1497,7 @@ extern "C" int dcf_bn_train_fwd(int dtype, const void *x, const float *gamma, co
     do {                                                                                                                                           \
         DCF_LAUNCH("bn_stats_partial", s, hipLaunchKernelGGL((k_bn_partial<T, false, V_>), dim3(nblk), dim3(256), 0, s, (const T *)x, \
                                                               (const T *)nullptr, (const float *)nullptr, (const float *)nullptr, partial, nvec, cg, stride)); \
-        DCF_LAUNCH("bn_stats_final", s, hipLaunchKernelGGL(k_bn_stats_final, dim3(C), dim3(64), 0, s, partial, nblk, C, (double)npix, eps,         \
+        DCF_LAUNCH("bn_stats_final", s, hipLaunchKernelGGL(k_bn_stats_final<T>, dim3(C), dim3(64), 0, s, (const T *)x, partial, nblk, C, (double)npix, eps, \
                                                             momentum, mean, invstd, running_mean, running_var));                                   \
         DCF_LAUNCH("bn_apply_fwd", s, hipLaunchKernelGGL((k_bn_apply_fwd<T, V_>), dim3(cdiv(nvec, 256)), dim3(256), 0, s, (const T *)x, mean, invstd, gamma, beta, \
                                                           (const T *)res, (T *)y, nvec, cg, relu));                                                \
