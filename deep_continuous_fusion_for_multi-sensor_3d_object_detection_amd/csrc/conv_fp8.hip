@@ -16,16 +16,19 @@ namespace {
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-// power-of-two scale that maps an absolute maximum of `amax` to at most 224 (half the e4m3 range of 448: the amax is
-// the previous step's).  Exact bit arithmetic, so every kernel (and the CPU oracle) derives the same value.
+// The activation scale rule (include/dcf_hip.h): the largest power of two s <= 2^126 with amax * s <= 224 (half the e4m3
+// range of 448: the amax is the previous step's); 1 when amax is not a positive finite number.  The exponent field of the
+// rounded quotient 224 / amax is the exponent of the exact one (a quotient just below a power of two never rounds up to it:
+// amax one ulp above 224 * 2^-k gives 2^k * (1 - 1.14 * 2^-24)), and the cap at 2^126 covers the quotients that overflow
+// (amax < 224 / FLT_MAX) and keeps 1 / s a normal number.  Bit arithmetic: every kernel and the host derive the same value.
 __host__ __device__ __forceinline__ float f8_act_scale(float amax)
 {
-    if (!(amax > 0.f) || !(amax < 3.0e38f)) return 1.f;
+    if (!(amax > 0.f) || !(amax <= 3.4028235e38f)) return 1.f;
     const float s = 224.f / amax;
     unsigned u;
     memcpy(&u, &s, 4);
     u &= 0x7F800000u;
-    if (u == 0u) return 1.1754944e-38f;          // 224/amax below the normal range: smallest normal power of two
+    if (u > 0x7E800000u) u = 0x7E800000u;        // 2^126
     float r;
     memcpy(&r, &u, 4);
     return r;
@@ -36,7 +39,19 @@ __device__ __forceinline__ float stored(float v, const float *) { return v; }
 __device__ __forceinline__ float stored(float v, const bf16_t *) { return bf2f(f2bf(v)); }
 __device__ __forceinline__ float stored(float v, const f16_t *) { return h2f(f2h(v)); }
 
-__device__ __forceinline__ float clamp448(float v) { return fminf(fmaxf(v, -448.f), 448.f); }
+// Saturation to the e4m3 range (+-Inf -> +-448) that leaves NaN alone: two compares and selects, not fminf / fmaxf, which
+// return their other operand for a NaN (-448 here).  v_cvt_pk_fp8_f32 turns the NaN into an e4m3 NaN code.
+__device__ __forceinline__ float clamp448(float v)
+{
+    v = v > 448.f ? 448.f : v;
+    return v < -448.f ? -448.f : v;
+}
+// |v| for the running maxima, 0 for Inf and NaN: the recorded maximum is the largest FINITE magnitude of the tensor
+__device__ __forceinline__ float finite_abs(float v)
+{
+    const float f = fabsf(v);
+    return f <= 3.4028235e38f ? f : 0.f;
+}
 __device__ __forceinline__ unsigned pack4_f8(float a, float b, float c, float d)
 {
     int w = 0;
@@ -46,8 +61,8 @@ __device__ __forceinline__ unsigned pack4_f8(float a, float b, float c, float d)
 }
 
 // ------------------------------------------------------------------------------------ activation cast
-// x8 = q(x * sx), sx = f8_act_scale(*amax_prev); amax_cur[64] = partial maxima of |x| (slot = workgroup & 63: one hot
-// address would serialise the workgroups' atomics).  8 elements per thread per pass.
+// x8 = q(x * sx), sx = f8_act_scale(*amax_prev); amax_cur[64] = partial maxima of the finite |x| (slot = workgroup & 63: one
+// hot address would serialise the workgroups' atomics).  8 elements per thread per pass.
 template <typename T>
 __global__ void __launch_bounds__(256) k_cast_f8(const T *x, unsigned *x8, const float *amax_prev, unsigned *amax_cur, int64_t n8)
 {
@@ -56,8 +71,8 @@ __global__ void __launch_bounds__(256) k_cast_f8(const T *x, unsigned *x8, const
     float am = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n8; i += (int64_t)gridDim.x * 256) {
         const float4 a = ld4(x + i * 8), b = ld4(x + i * 8 + 4);
-        am = fmaxf(am, fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(a.z), fabsf(a.w))));
-        am = fmaxf(am, fmaxf(fmaxf(fabsf(b.x), fabsf(b.y)), fmaxf(fabsf(b.z), fabsf(b.w))));
+        am = fmaxf(am, fmaxf(fmaxf(finite_abs(a.x), finite_abs(a.y)), fmaxf(finite_abs(a.z), finite_abs(a.w))));
+        am = fmaxf(am, fmaxf(fmaxf(finite_abs(b.x), finite_abs(b.y)), fmaxf(finite_abs(b.z), finite_abs(b.w))));
         uint2 o;
         o.x = pack4_f8(a.x * sx, a.y * sx, a.z * sx, a.w * sx);
         o.y = pack4_f8(b.x * sx, b.y * sx, b.z * sx, b.w * sx);
@@ -70,7 +85,7 @@ __global__ void __launch_bounds__(256) k_cast_f8(const T *x, unsigned *x8, const
     __syncthreads();
     if (threadIdx.x == 0) {
         am = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-        if (am > 0.f && am < 3.0e38f) atomicMax(amax_cur + (blockIdx.x & 63), __float_as_uint(am));     // non-negative floats order like their bits
+        if (am > 0.f) atomicMax(amax_cur + (blockIdx.x & 63), __float_as_uint(am));     // non-negative floats order like their bits
     }
 }
 
@@ -340,7 +355,7 @@ __global__ void __launch_bounds__(256) k_conv_f8(Conv8Args a)
                     // the image is made from the value as stored (rounded to TO): identical to dcf_cast_fp8 of y
                     float t[8];
 #pragma unroll
-                    for (int k = 0; k < 8; ++k) { t[k] = stored(v[k], y); am = fmaxf(am, fabsf(t[k])); }
+                    for (int k = 0; k < 8; ++k) { t[k] = stored(v[k], y); am = fmaxf(am, finite_abs(t[k])); }
                     uint2 q8;
                     q8.x = pack4_f8(t[0] * sy, t[1] * sy, t[2] * sy, t[3] * sy);
                     q8.y = pack4_f8(t[4] * sy, t[5] * sy, t[6] * sy, t[7] * sy);
@@ -357,7 +372,7 @@ __global__ void __launch_bounds__(256) k_conv_f8(Conv8Args a)
         __syncthreads();
         if (tid == 0) {
             am = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
-            if (am > 0.f && am < 3.0e38f) atomicMax(a.y8cur + (blockIdx.x & 63), __float_as_uint(am));
+            if (am > 0.f) atomicMax(a.y8cur + (blockIdx.x & 63), __float_as_uint(am));
         }
     }
 }

@@ -355,11 +355,17 @@ int dcf_wgrad_finalize_rows(const dcf_conv_param *table, int nconv, const int32_
  * v_mfma_scale_f32_32x32x64_f8f6f4; weights carry one scale per output channel, activations one power-of-two scale per
  * tensor derived on the device from the tensor's absolute maximum one step earlier (delayed scaling, no host sync):
  *   y = act((sum_k q(x*sx) q(w*sw[co])) / (sx*sw[co]) + shift[co] + res)
- * dcf_fp8_act_scale: the scale rule (largest power of two s with amax*s <= 224; 1 when amax is 0 / not finite). */
+ * dcf_fp8_act_scale: the scale rule -- the largest power of two s <= 2^126 with amax*s <= 224 for every positive finite
+ * amax (subnormals and FLT_MAX included), 1 when amax is zero, negative, Inf or NaN.  The cap keeps the scale finite for
+ * amax < 224 / FLT_MAX and 1/s a normal number.  Host and kernels derive the same bits.
+ * q(): round to nearest even on the e4m3 grid after saturation: |v| > 448 and +-Inf become +-448; NaN stays NaN (either
+ * e4m3 NaN code) in dcf_cast_fp8 and in the y8 image of dcf_conv2d_fwd_fp8 alike, and a NaN operand makes every output
+ * whose window covers it NaN (a ReLU epilogue is max(v, 0) as in the 16-bit kernels and returns 0 for it).
+ * Recorded maxima (amax_cur, y8cur) are the largest FINITE magnitude: Inf and NaN elements are left out one by one. */
 int dcf_fp8_act_scale(float amax, float *scale);
 /* x8[i] = q(x[i] * dcf_fp8_act_scale(*amax_prev)) (amax_prev null: scale 1).  amax_cur (optional): 64 device floats
- * holding partial maxima of |x| -- each workgroup raises one of them, so the tensor's maximum is the max over the 64
- * (one hot address would serialise the atomics).  n multiple of 8. */
+ * holding partial maxima of the finite |x| -- each workgroup raises one of them (never lowers it), so the tensor's maximum
+ * is the max over the 64 (one hot address would serialise the atomics).  n multiple of 8. */
 int dcf_cast_fp8(int dtype, const void *x, void *x8, const float *amax_prev, float *amax_cur, int64_t n, dcf_stream_t stream);
 /* Per-conv fp8 weight images: w8 [cout_pad][taps][cin] = q(bn_scale*W * 448/amax_co) at byte offset w8_off of w8arena,
  * dequantisation factors amax_co/448 at element offset wscale_off of wsarena (w8_off < 0: conv not on the fp8 path:

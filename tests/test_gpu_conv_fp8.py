@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from _fp8_ref import act_scale_exact, scale_rule_values
 from _util import TORCH_DT, from_dev, pkg, rnd, to_dev
 
 pytestmark = pytest.mark.gpu
@@ -24,22 +25,16 @@ def bits8(t):
     return t.to(torch.float8_e4m3fn).view(torch.uint8)
 
 
-def act_scale_ref(amax):
-    a = np.float32(amax)
-    if not (a > 0 and np.isfinite(a)):
-        return 1.0
-    s = np.float32(224.0) / a
-    u = np.frombuffer(np.float32(s).tobytes(), dtype=np.uint32)[0] & np.uint32(0x7F800000)
-    return float(np.frombuffer(np.uint32(u).tobytes(), dtype=np.float32)[0])
-
-
 def test_act_scale_rule():
     ops = pkg("ops")
     for amax in (0.0, 1e-30, 0.013, 0.5, 1.0, 3.7, 223.9, 224.0, 224.1, 448.0, 1e4, float("inf"), float("nan")):
         s = ops.fp8_act_scale(amax)
-        assert s == act_scale_ref(amax)
+        assert s == act_scale_exact(amax)
         if 0 < amax < 1e30:
             assert amax * s <= 224.0 < amax * s * 2 and np.log2(s) == int(np.log2(s))
+    # the exact rule (tests/_fp8_ref.py) on every 224 * 2^-k with its fp32 neighbours, the tiny maxima whose quotient overflows, FLT_MAX
+    for amax in scale_rule_values():
+        assert ops.fp8_act_scale(amax) == act_scale_exact(amax), amax
 
 
 @pytest.mark.parametrize("dtype", [1, 2, 0])
@@ -53,7 +48,7 @@ def test_cast_fp8_bits_and_amax(dtype):
         prev = None if amax_prev is None else torch.tensor([amax_prev], dtype=torch.float32, device="cuda")
         cur = torch.full((64,), 0.25, dtype=torch.float32, device="cuda")
         x8 = ops.cast_fp8(dtype, xd, prev, cur)
-        s = act_scale_ref(amax_prev or 0.0)
+        s = act_scale_exact(amax_prev or 0.0)
         want = bits8((xq * s).clamp(-448.0, 448.0))
         assert torch.equal(x8.cpu(), want)
         assert float(cur.max().item()) == float(xq.abs().max()) and float(cur.min().item()) >= 0.25
@@ -100,7 +95,7 @@ def test_conv_fp8_matches_quantised_reference(case, out_dtype):
     w = rnd((Cout, Cin, k, k), 6, -0.08, 0.08) * torch.linspace(0.2, 3.0, Cout).view(-1, 1, 1, 1)     # channel-dependent ranges
     shift = rnd((Cout,), 7, -0.5, 0.5)
     amax = float(x.abs().max()) * 1.3                       # "previous step" maximum: not this tensor's own
-    sx = act_scale_ref(amax)
+    sx = act_scale_exact(amax)
     wamax = w.abs().amax(dim=(1, 2, 3))
     sw = np.float32(448.0) / wamax
     wq = q8(w * sw.view(-1, 1, 1, 1))
