@@ -86,6 +86,13 @@ SIGNATURES = {
     "dcf_eval_accumulate": (c_int, [P, P, P, P, P, c_int, P, c_int, P, P, c_i64, P, P]),
     "dcf_eval_ap_workspace_bytes": (c_size_t, [c_i64]),
     "dcf_eval_ap": (c_int, [P, P, P, c_i64, c_int, P, P, P, P]),
+    # eval_protocol: kitti (csrc/evalpost.hip, k_kitti_*)
+    "dcf_eval_det_flags": (c_int, [P, P, c_int, P, P, c_int, c_int, c_int, P, ctypes.c_double, P, P]),
+    "dcf_eval_iou_levels": (c_int, [P, P, P, c_int, P, c_int, P, P, P]),
+    "dcf_eval_match_levels": (c_int, [P, P, P, P, c_int, P, P, c_int, P, P, c_int, P, P, P]),
+    "dcf_eval_accumulate_levels": (c_int, [P, P, P, P, P, P, c_int, P, P, c_int, P, P, P, c_i64, P, P]),
+    "dcf_eval_ap_levels_workspace_bytes": (c_size_t, [c_i64]),
+    "dcf_eval_ap_levels": (c_int, [P, P, P, P, c_i64, c_int, P, P, P, P, P]),
     "dcf_wgrad_finalize_rows": (c_int, [P, c_int, P, P, P, P, P, P, P, c_float, P]),
     "dcf_bn_workspace_bytes": (c_size_t, [c_int]),
     "dcf_bn_train_fwd": (c_int, [c_int, P, P, P, P, P, P, P, P, P, c_i64, c_int, c_float, c_float, c_int, P, P]),

@@ -566,3 +566,357 @@ extern "C" int dcf_eval_ap(const float *acc_scores, const uint32_t *acc_tpmask, 
                                                       (long long *)out_counts));
     return DCF_OK;
 }
+
+// ------------------------------------------------------------------ KITTI-style protocol (eval_protocol: kitti)
+// The third outcome (ignored), the difficulty dimension and the z axis on top of the ranked evaluation above; evalkitti.py is the
+// host statement.  Mask words carry bit 10 d + t for difficulty d (easy, moderate, hard) and threshold t, one word per metric
+// (bird's-eye, 3-D).  The kernels above are not touched.
+namespace {
+
+constexpr int EV_BITS = 10;              // bits per difficulty in a mask word
+
+struct EvFlagParam {                     // by value: nothing has to reach the device first
+    float C[12];                         // the frame's [4][3] projection matrix, row-major: [x, y, z, 1] . C = (u d, v d, d)
+    double H, W;                         // image size the 2-D box is clamped to
+    double min_height[3];
+    double overlap;
+};
+
+// flags[i]: bit d iff the projected height of candidate i is below min_height[d]; bit 3 iff more than `overlap` of its 2-D box lies
+// in one DontCare rectangle (evalkitti.det_flags).  fp64 on the fp32 entries, in the stated order (no contraction).
+__global__ void __launch_bounds__(256) k_kitti_flags(const float *boxes, const int *count, int n_max, EvFlagParam p, const float *dontcare, int D, unsigned *flags)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int n = min(*count, n_max);
+    if (i >= n) return;
+    const float *b = boxes + (size_t)i * 7;
+    double rect[4][2];
+    ev_rect(b, rect);
+    const double z = b[2], h = b[5];
+    const double inf = __longlong_as_double(0x7ff0000000000000ll);
+    double umin = inf, vmin = inf, umax = -inf, vmax = -inf;
+    int front = 0;
+    for (int s = 0; s < 2; ++s) {
+        const double zz = s == 0 ? z - h / 2 : z + h / 2;
+        for (int k = 0; k < 4; ++k) {
+            const double x = rect[k][0], y = rect[k][1];
+            const double d = ((x * (double)p.C[2] + y * (double)p.C[5]) + zz * (double)p.C[8]) + (double)p.C[11];
+            if (!(d > 0)) continue;
+            ++front;
+            const double ud = ((x * (double)p.C[0] + y * (double)p.C[3]) + zz * (double)p.C[6]) + (double)p.C[9];
+            const double vd = ((x * (double)p.C[1] + y * (double)p.C[4]) + zz * (double)p.C[7]) + (double)p.C[10];
+            const double u = fmin(fmax(ud / d, 0.0), p.W), v = fmin(fmax(vd / d, 0.0), p.H);
+            umin = fmin(umin, u); umax = fmax(umax, u);
+            vmin = fmin(vmin, v); vmax = fmax(vmax, v);
+        }
+    }
+    double height = 0.0, area = 0.0;
+    if (front > 0) { height = vmax - vmin; area = (umax - umin) * height; }
+    unsigned f = 0;
+    for (int d = 0; d < 3; ++d)
+        if (height < p.min_height[d]) f |= 1u << d;
+    if (area > 0) {
+        for (int q = 0; q < D; ++q) {
+            const float *rc = dontcare + (size_t)q * 4;
+            const double iw = fmin(umax, (double)rc[2]) - fmax(umin, (double)rc[0]);
+            const double ih = fmin(vmax, (double)rc[3]) - fmax(vmin, (double)rc[1]);
+            if (iw > 0 && ih > 0 && iw * ih / area > p.overlap) { f |= 8u; break; }
+        }
+    }
+    flags[i] = f;
+}
+
+// iou_bev[i][r], iou_3d[i][r] of candidate i (a survivor) with labelled row r, both from one clip; NaN where there is no pair
+__global__ void __launch_bounds__(256) k_kitti_iou(const float *boxes, const int32_t *keep, const int *count, int n_max, const float *refs, int R, double *iou_bev,
+                                                   double *iou_3d)
+{
+    const int n = min(*count, n_max);
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int i = (int)(t / R), r = (int)(t - (long long)i * R);
+    if (i >= n) return;
+    double vb = __longlong_as_double(0x7ff8000000000000ll), v3 = vb;
+    const float *pb = boxes + (size_t)i * 7, *rb = refs + (size_t)r * 9;
+    if (keep[i] != 0 && rb[8] == 1.0f) {
+        double r1[4][2], r2[4][2], poly[12][2];
+        ev_rect(pb, r1);
+        ev_rect(rb, r2);
+        const int nv = ev_clip(r1, r2, poly);
+        const double ia = nv >= 3 ? ev_shoelace(poly, nv) : 0.0;
+        const double a1 = ev_shoelace(r1, 4), a2 = ev_shoelace(r2, 4);
+        vb = ia / (a1 + a2 - ia);
+        const double z1 = pb[2], h1 = pb[5], z2 = rb[2], h2 = rb[5];
+        const double zov = fmax(0.0, fmin(z1 + h1 / 2, z2 + h2 / 2) - fmax(z1 - h1 / 2, z2 - h2 / 2));
+        const double iv = ia * zov;
+        v3 = iv / (a1 * h1 + a2 * h2 - iv);
+    }
+    iou_bev[(size_t)i * R + r] = vb;
+    iou_3d[(size_t)i * R + r] = v3;
+}
+
+// One workgroup per (metric, difficulty), k_rank_match's shape inside: one wave per threshold walks the survivors in rank order.
+// (A) the best counted row not yet taken, a true positive iff its IoU > t; else (B) ignored iff an ignored row has IoU > t; else (C)
+// ignored iff flag bit d or 3 is set.  Each workgroup owns one 10-bit field of the output words (zeroed by the entry): an integer OR.
+__global__ void __launch_bounds__(1024) k_kitti_match(const double *iou_bev, const double *iou_3d, const int32_t *keep, const int *count, int n_max, const float *refs,
+                                                      const int32_t *levels, int R, const unsigned *flags, const double *thr, int nthr, unsigned *tpmask,
+                                                      unsigned *igmask)
+{
+    __shared__ unsigned tp_s[EV_CAP], ig_s[EV_CAP];
+    const int m = blockIdx.x / 3, d = blockIdx.x - 3 * m;
+    const double *iou = m == 0 ? iou_bev : iou_3d;
+    const int n = min(min(*count, n_max), EV_CAP);
+    for (int q = threadIdx.x; q < n; q += blockDim.x) { tp_s[q] = 0u; ig_s[q] = 0u; }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (wave < nthr) {
+        const double t = thr[wave];
+        unsigned long long counted = 0ull, ignored = 0ull, taken = 0ull;      // bit k: row lane + 64 k
+        for (int r = lane, k = 0; r < R; r += 64, ++k) {
+            if (refs[(size_t)r * 9 + 8] != 1.0f) continue;
+            const int lv = levels ? levels[r] : 0;
+            if (lv <= d) counted |= 1ull << k; else ignored |= 1ull << k;
+        }
+        const unsigned fbits = (1u << d) | 8u;
+        for (int i = 0; i < n; ++i) {
+            if (keep[i] == 0) continue;
+            double best = -__longlong_as_double(0x7ff0000000000000ll);
+            int bestr = 0x7fffffff;
+            const unsigned long long open = counted & ~taken;
+            for (int r = lane, k = 0; r < R; r += 64, ++k) {
+                if (!((open >> k) & 1ull)) continue;
+                const double v = iou[(size_t)i * R + r];
+                if (v > best) { best = v; bestr = r; }           // NaN never wins; ascending r keeps the lower row on a tie
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const double ob = __shfl_xor(best, o, 64);
+                const int orow = __shfl_xor(bestr, o, 64);
+                if (ob > best || (ob == best && orow < bestr)) { best = ob; bestr = orow; }
+            }
+            if (best > t && bestr < R) {                         // the same on every lane
+                if ((bestr & 63) == lane) taken |= 1ull << (bestr >> 6);
+                if (lane == 0) atomicOr(&tp_s[i], 1u << wave);
+            } else {
+                bool hit = false;
+                for (int r = lane, k = 0; r < R; r += 64, ++k)
+                    if (((ignored >> k) & 1ull) && iou[(size_t)i * R + r] > t) hit = true;
+                const bool ig = __ballot(hit) != 0ull || (flags[i] & fbits) != 0u;
+                if (ig && lane == 0) atomicOr(&ig_s[i], 1u << wave);
+            }
+        }
+    }
+    __syncthreads();
+    for (int q = threadIdx.x; q < n; q += blockDim.x) {
+        if (tp_s[q]) atomicOr(&tpmask[(size_t)m * n_max + q], tp_s[q] << (EV_BITS * d));
+        if (ig_s[q]) atomicOr(&igmask[(size_t)m * n_max + q], ig_s[q] << (EV_BITS * d));
+    }
+}
+
+// Order-preserving append of one sample's survivors (score, tpmask[2], igmask[2]) at the cursor; state = {cursor, n_gt[3], truncated
+// samples, -, -, -}.  The cursor keeps counting past the capacity (the summary raises then); nothing past it is written.
+__global__ void __launch_bounds__(1024) k_kitti_accumulate(const float *scores, const unsigned *tpmask, const unsigned *igmask, const int32_t *keep, const int *count,
+                                                           const int *total, int n_max, const float *refs, const int32_t *levels, int R, float *acc_scores,
+                                                           unsigned *acc_tp, unsigned *acc_ig, long long capacity, long long *state)
+{
+    __shared__ int wsum[16];
+    __shared__ long long base_s;
+    __shared__ int ngt_s[3];
+    const int n = min(*count, n_max);
+    if (threadIdx.x == 0) { base_s = state[0]; ngt_s[0] = 0; ngt_s[1] = 0; ngt_s[2] = 0; }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int c0 = 0; c0 < n; c0 += 1024) {
+        const int i = c0 + threadIdx.x;
+        const bool ok = i < n && keep[i] != 0;
+        const unsigned long long bal = __ballot(ok);
+        const int before = __popcll(bal & ((1ull << lane) - 1));
+        if (lane == 0) wsum[wave] = __popcll(bal);
+        __syncthreads();
+        long long pos = base_s + before;
+        for (int w = 0; w < wave; ++w) pos += wsum[w];
+        if (ok && pos >= 0 && pos < capacity) {
+            acc_scores[pos] = scores[i];
+            for (int m = 0; m < 2; ++m) {
+                acc_tp[(size_t)m * capacity + pos] = tpmask[(size_t)m * n_max + i];
+                acc_ig[(size_t)m * capacity + pos] = igmask[(size_t)m * n_max + i];
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) { int tot = 0; for (int w = 0; w < 16; ++w) tot += wsum[w]; base_s += tot; }
+        __syncthreads();
+    }
+    for (int r0 = 0; r0 < R; r0 += 1024) {
+        const int r = r0 + threadIdx.x;
+        const bool valid = r < R && refs[(size_t)r * 9 + 8] == 1.0f;
+        const int lv = valid && levels ? levels[r] : 0;
+        for (int d = 0; d < 3; ++d) {
+            const unsigned long long bal = __ballot(valid && lv <= d);
+            if (lane == 0) atomicAdd(&ngt_s[d], (int)__popcll(bal));
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        state[0] = base_s;
+        for (int d = 0; d < 3; ++d) state[1 + d] += ngt_s[d];
+        if (*total > n_max) state[4] += 1;
+    }
+}
+
+// k_ap_rank for the four mask arrays: sorted [4][capacity] = tpmask[0], tpmask[1], igmask[0], igmask[1] in global rank order
+__global__ void __launch_bounds__(256) k_kitti_ap_rank(const float *acc_scores, const unsigned *acc_tp, const unsigned *acc_ig, const long long *state,
+                                                       long long capacity, unsigned *sorted)
+{
+    __shared__ unsigned long long tile[EV_TILE];
+    const int n = (int)max(0ll, min(state[0], capacity));
+    if ((int)(blockIdx.x * 256) >= n) return;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const unsigned long long mine = i < n ? ev_key(acc_scores[i], (unsigned)i) : ~0ull;
+    int rank = 0;
+    for (int j0 = 0; j0 < n; j0 += EV_TILE) {
+        __syncthreads();
+        for (int q = threadIdx.x; q < EV_TILE; q += 256) tile[q] = j0 + q < n ? ev_key(acc_scores[j0 + q], (unsigned)(j0 + q)) : 0ull;
+        __syncthreads();
+#pragma unroll 8
+        for (int q = 0; q < EV_TILE; ++q) rank += tile[q] > mine ? 1 : 0;
+    }
+    if (i < n && rank < n) {
+        for (int m = 0; m < 2; ++m) {
+            sorted[(size_t)m * capacity + rank] = acc_tp[(size_t)m * capacity + i];
+            sorted[(size_t)(2 + m) * capacity + rank] = acc_ig[(size_t)m * capacity + i];
+        }
+    }
+}
+
+// One workgroup per (metric, difficulty, threshold): k_ap_curve with a second scan.  k counts the detections not ignored here, c the
+// true positives among them; p = c / k enters the level reached by 40 c / n_gt[d] for the detections that stay.
+__global__ void __launch_bounds__(1024) k_kitti_ap_curve(const unsigned *sorted, const long long *state, long long capacity, int nthr, double *out_ap,
+                                                         long long *out_tp, long long *out_ig)
+{
+    __shared__ unsigned long long M[EV_LEVELS + 1];
+    __shared__ int wsum_c[16], wsum_k[16];
+    __shared__ long long carry_c, carry_k;
+    const int blk = blockIdx.x, m = blk / (3 * nthr), d = (blk / nthr) % 3, t = blk % nthr;
+    const int sh = EV_BITS * d + t;
+    const unsigned *tp = sorted + (size_t)m * capacity, *ig = sorted + (size_t)(2 + m) * capacity;
+    const int n = (int)max(0ll, min(state[0], capacity));
+    const long long n_gt = state[1 + d];
+    if (threadIdx.x <= EV_LEVELS) M[threadIdx.x] = 0ull;
+    if (threadIdx.x == 0) { carry_c = 0; carry_k = 0; }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int c0 = 0; c0 < n; c0 += 1024) {
+        const int q = c0 + threadIdx.x;
+        const bool stay = q < n && !((ig[q] >> sh) & 1u);
+        const bool bit = stay && ((tp[q] >> sh) & 1u);
+        const unsigned long long balc = __ballot(bit), balk = __ballot(stay);
+        const unsigned long long upto = (2ull << lane) - 1;
+        const int inclc = __popcll(balc & upto), inclk = __popcll(balk & upto);
+        if (lane == 0) { wsum_c[wave] = __popcll(balc); wsum_k[wave] = __popcll(balk); }
+        __syncthreads();
+        long long c = carry_c + inclc, k = carry_k + inclk;
+        for (int w = 0; w < wave; ++w) { c += wsum_c[w]; k += wsum_k[w]; }
+        if (stay && n_gt > 0) {
+            const double p = (double)c / (double)k;
+            const long long j = min((long long)EV_LEVELS, 40 * c / n_gt);
+            atomicMax(&M[j], (unsigned long long)__double_as_longlong(p));
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            int totc = 0, totk = 0;
+            for (int w = 0; w < 16; ++w) { totc += wsum_c[w]; totk += wsum_k[w]; }
+            carry_c += totc; carry_k += totk;
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        double ap = __longlong_as_double(0x7ff8000000000000ll);
+        if (n_gt > 0) {
+            double sum = 0.0;
+            for (int j = 1; j <= EV_LEVELS; ++j) {
+                unsigned long long mx = 0ull;
+                for (int q = j; q <= EV_LEVELS; ++q) mx = max(mx, M[q]);
+                sum += __longlong_as_double((long long)mx);
+            }
+            ap = sum / 40.0;
+        }
+        out_ap[blk] = ap;
+        out_tp[blk] = carry_c;
+        out_ig[blk] = (long long)n - carry_k;
+    }
+}
+
+}  // namespace
+
+extern "C" int dcf_eval_det_flags(const float *boxes, const int32_t *count_dev, int n_max, const float *crt_host, const float *dontcare, int D, int image_h,
+                                  int image_w, const double *min_height_host, double overlap, uint32_t *flags, dcf_stream_t stream)
+{
+    DCF_REQUIRE(boxes && count_dev && crt_host && min_height_host && flags && n_max > 0 && n_max <= EV_CAP && D >= 0 && D <= 4096 && image_h > 0 && image_w > 0,
+                "dcf_eval_det_flags: at most %d boxes and 4096 DontCare rectangles per call (got %d, %d)", EV_CAP, n_max, D);
+    DCF_REQUIRE(D == 0 || dontcare, "dcf_eval_det_flags: null DontCare rectangles");
+    DCF_REQUIRE(overlap > 0.0 && overlap <= 1.0, "dcf_eval_det_flags: overlap must be in (0, 1]");
+    EvFlagParam p;
+    for (int k = 0; k < 12; ++k) p.C[k] = crt_host[k];
+    for (int d = 0; d < 3; ++d) p.min_height[d] = min_height_host[d];
+    p.H = (double)image_h; p.W = (double)image_w; p.overlap = overlap;
+    hipStream_t s = S(stream);
+    DCF_LAUNCH("eval_kitti_flags", s, hipLaunchKernelGGL(k_kitti_flags, dim3(cdiv(n_max, 256)), dim3(256), 0, s, boxes, count_dev, n_max, p, dontcare, D, flags));
+    return DCF_OK;
+}
+
+extern "C" int dcf_eval_iou_levels(const float *boxes, const int32_t *keep, const int32_t *count_dev, int n_max, const float *refs, int R, double *iou_bev,
+                                   double *iou_3d, dcf_stream_t stream)
+{
+    DCF_REQUIRE(boxes && keep && count_dev && n_max > 0 && n_max <= EV_CAP && R >= 0 && R <= 4096,
+                "dcf_eval_iou_levels: at most %d boxes and 4096 label rows per call (got %d, %d)", EV_CAP, n_max, R);
+    if (R == 0) return DCF_OK;
+    DCF_REQUIRE(refs && iou_bev && iou_3d, "dcf_eval_iou_levels: null label rows or matrices");
+    hipStream_t s = S(stream);
+    DCF_LAUNCH("eval_kitti_iou", s, hipLaunchKernelGGL(k_kitti_iou, dim3(cdiv((int64_t)n_max * R, 256)), dim3(256), 0, s, boxes, keep, count_dev, n_max, refs, R, iou_bev, iou_3d));
+    return DCF_OK;
+}
+
+extern "C" int dcf_eval_match_levels(const double *iou_bev, const double *iou_3d, const int32_t *keep, const int32_t *count_dev, int n_max, const float *refs,
+                                     const int32_t *levels, int R, const uint32_t *flags, const double *thresholds_dev, int nthr, uint32_t *tpmask,
+                                     uint32_t *igmask, dcf_stream_t stream)
+{
+    DCF_REQUIRE(keep && count_dev && flags && thresholds_dev && tpmask && igmask && n_max > 0 && n_max <= EV_CAP && R >= 0 && R <= 4096 && nthr >= 1 && nthr <= EV_BITS,
+                "dcf_eval_match_levels: at most %d boxes, 4096 label rows and %d thresholds per call (got %d, %d, %d)", EV_CAP, EV_BITS, n_max, R, nthr);
+    DCF_REQUIRE(R == 0 || (refs && iou_bev && iou_3d), "dcf_eval_match_levels: null label rows or matrices");
+    hipStream_t s = S(stream);
+    DCF_HIP(hipMemsetAsync(tpmask, 0, sizeof(uint32_t) * 2 * (size_t)n_max, s));
+    DCF_HIP(hipMemsetAsync(igmask, 0, sizeof(uint32_t) * 2 * (size_t)n_max, s));
+    DCF_LAUNCH("eval_kitti_match", s, hipLaunchKernelGGL(k_kitti_match, dim3(6), dim3(64 * nthr), 0, s, iou_bev, iou_3d, keep, count_dev, n_max, refs, levels, R, flags,
+                                                         thresholds_dev, nthr, tpmask, igmask));
+    return DCF_OK;
+}
+
+extern "C" int dcf_eval_accumulate_levels(const float *scores, const uint32_t *tpmask, const uint32_t *igmask, const int32_t *keep, const int32_t *count_dev,
+                                          const int32_t *total_dev, int n_max, const float *refs, const int32_t *levels, int R, float *acc_scores,
+                                          uint32_t *acc_tpmask, uint32_t *acc_igmask, int64_t capacity, int64_t *state, dcf_stream_t stream)
+{
+    DCF_REQUIRE(scores && tpmask && igmask && keep && count_dev && total_dev && acc_scores && acc_tpmask && acc_igmask && state && n_max > 0 && n_max <= EV_CAP &&
+                R >= 0 && capacity > 0 && capacity <= (1 << 30), "dcf_eval_accumulate_levels: bad arguments");
+    DCF_REQUIRE(R == 0 || refs, "dcf_eval_accumulate_levels: null label rows");
+    hipStream_t s = S(stream);
+    DCF_LAUNCH("eval_kitti_accumulate", s, hipLaunchKernelGGL(k_kitti_accumulate, dim3(1), dim3(1024), 0, s, scores, tpmask, igmask, keep, count_dev, total_dev, n_max, refs,
+                                                              levels, R, acc_scores, acc_tpmask, acc_igmask, (long long)capacity, (long long *)state));
+    return DCF_OK;
+}
+
+extern "C" size_t dcf_eval_ap_levels_workspace_bytes(int64_t capacity)
+{
+    return 16 * (size_t)(capacity > 0 ? capacity : 0) + 64;
+}
+
+extern "C" int dcf_eval_ap_levels(const float *acc_scores, const uint32_t *acc_tpmask, const uint32_t *acc_igmask, const int64_t *state, int64_t capacity, int nthr,
+                                  double *out_ap, int64_t *out_tp, int64_t *out_ignored, void *ws, dcf_stream_t stream)
+{
+    DCF_REQUIRE(acc_scores && acc_tpmask && acc_igmask && state && out_ap && out_tp && out_ignored && ws && capacity > 0 && capacity <= (1 << 30) && nthr >= 1 &&
+                nthr <= EV_BITS, "dcf_eval_ap_levels: bad arguments");
+    hipStream_t s = S(stream);
+    unsigned *sorted = (unsigned *)ws;
+    DCF_LAUNCH("eval_kitti_ap_rank", s, hipLaunchKernelGGL(k_kitti_ap_rank, dim3(cdiv(capacity, 256)), dim3(256), 0, s, acc_scores, acc_tpmask, acc_igmask,
+                                                           (const long long *)state, (long long)capacity, sorted));
+    DCF_LAUNCH("eval_kitti_ap_curve", s, hipLaunchKernelGGL(k_kitti_ap_curve, dim3(6 * nthr), dim3(1024), 0, s, sorted, (const long long *)state, (long long)capacity, nthr,
+                                                            out_ap, (long long *)out_tp, (long long *)out_ignored));
+    return DCF_OK;
+}

@@ -71,8 +71,18 @@ def read_labels(path, calib, config, types=KITTI_CAR_TYPES):
     mx = int(config["max_num_bbox"])
     out = torch.zeros(mx, 9)
     n = 0
+    for row, _ in _label_rows(path, calib, config, types):
+        out[n] = row
+        n += 1
+    return out, n
+
+
+def _label_rows(path, calib, config, types):
+    """(row [9] f32, the line's fields) of the label lines read_labels keeps, in file order, at most max_num_bbox of them."""
+    mx = int(config["max_num_bbox"])
+    n = 0
     if not os.path.isfile(path):
-        return out, 0
+        return
     inv = np.linalg.inv(velo_to_rect(calib))
     with open(path) as f:
         for line in f:
@@ -85,9 +95,32 @@ def read_labels(path, calib, config, types=KITTI_CAR_TYPES):
             if not (config["lidar_x_min"] <= x < config["lidar_x_max"] and config["lidar_y_min"] <= y < config["lidar_y_max"]):
                 continue                                              # valid_bbox, data_import_carla.py:106-110
             yaw = wrap_yaw(-float(t[14]) - np.pi / 2.0)
-            out[n] = torch.tensor([x, y, z, l, w, h, yaw, CAR_CLASS, 1], dtype=torch.float32)
+            yield torch.tensor([x, y, z, l, w, h, yaw, CAR_CLASS, 1], dtype=torch.float32), t
             n += 1
-    return out, n
+
+
+def read_label_levels(path, calib, config, settings, types=KITTI_CAR_TYPES):
+    """What `eval_protocol: kitti` needs beside read_labels' rows: (bbox_level int32 [max_num_bbox], dontcare
+    f32 [eval_max_dontcare, 4]).  bbox_level[r] = evalkitti.difficulty_level of the line behind row r (2-D height = bottom - top,
+    occlusion, truncation; a Van is 3), 3 on the unused rows; dontcare = the (left, top, right, bottom) boxes of the DontCare
+    lines in file order, zero on the unused rows.  More DontCare lines than rows raises."""
+    from . import evalkitti as EK
+    levels = torch.full((int(config["max_num_bbox"]),), EK.NEVER, dtype=torch.int32)
+    for r, (_, t) in enumerate(_label_rows(path, calib, config, types)):
+        levels[r] = EK.difficulty_level(t[0], float(t[7]) - float(t[5]), int(float(t[2])), float(t[1]), settings)
+    dontcare = torch.zeros(settings["max_dontcare"], 4)
+    k = 0
+    if os.path.isfile(path):
+        with open(path) as f:
+            for line in f:
+                t = line.split()
+                if len(t) < 8 or t[0] != "DontCare":
+                    continue
+                if k >= settings["max_dontcare"]:
+                    raise ValueError("%s: more than eval_max_dontcare = %d DontCare lines (nothing is dropped silently)" % (path, settings["max_dontcare"]))
+                dontcare[k] = torch.tensor([float(v) for v in t[4:8]], dtype=torch.float32)
+                k += 1
+    return levels, dontcare
 
 
 def fit_image(rgb, H, W):
@@ -115,6 +148,12 @@ class KittiDataset(Dataset):
         velo = os.path.join(self.split_dir, "velodyne")
         self.ids = sorted(f[:-4] for f in os.listdir(velo) if f.endswith(".bin")) if os.path.isdir(velo) else []
         self._geometry = None
+        # `eval_protocol: kitti`: the sample also carries bbox_level and dontcare (validated here; None = today's five keys)
+        self._protocol = None
+        if (config.get("eval_protocol") or "plain") != "plain":
+            from . import evalkitti as EK
+            EK.protocol(config)
+            self._protocol = EK.settings(config)
 
     def __len__(self):
         return len(self.ids)
@@ -139,17 +178,27 @@ class KittiDataset(Dataset):
         image = fit_image(rgb, int(self.config["image_height"]), int(self.config["image_width"]))
         return torch.from_numpy(np.ascontiguousarray(pts)), image, boxes, n, torch.from_numpy(crt_from_calib(calib))
 
+    def read_levels(self, idx):
+        """(bbox_level, dontcare) of frame idx under `eval_protocol: kitti` (read_label_levels)."""
+        fid = self.ids[idx]
+        calib = read_calib(os.path.join(self.split_dir, "calib", fid + ".txt"))
+        return read_label_levels(os.path.join(self.split_dir, "label_2", fid + ".txt"), calib, self.config, self._protocol)
+
     def __getitem__(self, idx):
         if idx < 0 or idx >= len(self.ids):
             raise IndexError("idx is not in data file")
         pts, image, boxes, n, crt = self.read_frame(idx)
+        extra = {}
+        if self._protocol is not None:
+            extra["bbox_level"], extra["dontcare"] = self.read_levels(idx)
         if self.raw:
-            return {"image": image, "bboxes": boxes, "num_bboxes": n, "lidar_points": pts, "crt": crt}
+            return dict({"image": image, "bboxes": boxes, "num_bboxes": n, "lidar_points": pts, "crt": crt}, **extra)
         g = self.geometry
         voxel = g.voxelize(pts)
         pc, uv, cnt = g.project(pts, crt=crt.numpy())
         sample = {"image": image, "bboxes": boxes, "num_bboxes": n, "pointcloud_raw": pc, "projected_loc_uv": uv,
                   "num_points_raw": cnt, "pointcloud": voxel}
+        sample.update(extra)
         if self.want_bev_image:
             from . import ops
             pin, _, _ = ops.range_filter(pts.cuda(), g.grid.lim)

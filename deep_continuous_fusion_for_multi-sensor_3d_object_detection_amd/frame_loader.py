@@ -29,6 +29,9 @@ import torch
 from torch.utils.data import DataLoader
 
 
+OPTIONAL_LABEL_KEYS = ("bbox_level", "dontcare")
+
+
 def collate_raw(samples):
     """Raw samples -> one batch dict; point lists and images stay lists (they are packed straight into the pinned
     staging set), the small label tensors are stacked."""
@@ -37,6 +40,9 @@ def collate_raw(samples):
            "bboxes": torch.stack([s["bboxes"] for s in samples], 0),
            "num_bboxes": torch.tensor([int(s["num_bboxes"]) for s in samples]),
            "crt": [s["crt"] for s in samples] if samples and samples[0].get("crt") is not None else None}
+    for key in OPTIONAL_LABEL_KEYS:                      # `eval_protocol: kitti`: stacked, next to bboxes
+        if samples and key in samples[0]:
+            out[key] = torch.stack([s[key] for s in samples], 0)
     return out
 
 
@@ -148,6 +154,7 @@ class FrameLoader(object):
         B = len(host["points"])
         pts = st.pack(host, self._cap)
         out = Batch(bboxes=host["bboxes"], num_bboxes=host["num_bboxes"], crt=host["crt"])
+        out.update({key: host[key] for key in OPTIONAL_LABEL_KEYS if key in host})       # host tensors, like bboxes
         if consumer_stream is not None:
             self._copy.wait_stream(consumer_stream)
         elif st.consumed is not None:

@@ -1053,6 +1053,78 @@ def eval_ap(acc_scores, acc_tpmask, state, nthr):
     return ap, tp
 
 
+# ------------------------------------------------------------------ KITTI-style protocol (eval_protocol: kitti)
+def eval_det_flags(boxes, count, crt, dontcare, image_h, image_w, min_height, overlap):
+    """Flag bits of the candidates boxes [n,7] (count int32 [1] valid rows): bit d iff the projected height < min_height[d], bit 3 iff
+    more than `overlap` of the projected 2-D box lies in one rectangle of dontcare [D,4] (device, or None).  crt: the frame's [4,3]
+    matrix as a HOST array / tensor (it travels as a kernel argument).  Returns int32 [n] (the bits of a uint32)."""
+    n = boxes.shape[0]
+    flags = torch.zeros((max(n, 1),), dtype=torch.int32, device=boxes.device)
+    if n == 0:
+        return flags[:0]
+    crt = np.ascontiguousarray(crt.detach().cpu().numpy() if isinstance(crt, torch.Tensor) else crt, dtype=np.float32).reshape(12)
+    mh = np.ascontiguousarray(min_height, dtype=np.float64).reshape(3)
+    D = 0 if dontcare is None else dontcare.shape[0]
+    H.call("dcf_eval_det_flags", _chk(boxes, "boxes"), count, n, crt, _chk(dontcare, "dontcare") if D else None, D, int(image_h), int(image_w), mh,
+           float(overlap), flags, H.stream_ptr())
+    return flags
+
+
+def eval_iou_levels(boxes, keep, count, ref_boxes):
+    """(iou_bev, iou_3d) fp64 [n,R] of the survivors against the labelled rows of ref_boxes [R,9], both from one clip; NaN elsewhere
+    (rows >= count are left unwritten)."""
+    n, R = boxes.shape[0], ref_boxes.shape[0]
+    bev = torch.empty((n, R), dtype=torch.float64, device=boxes.device)
+    i3d = torch.empty((n, R), dtype=torch.float64, device=boxes.device)
+    if n and R:
+        H.call("dcf_eval_iou_levels", _chk(boxes, "boxes"), _chk(keep, "keep"), count, n, _chk(ref_boxes, "ref_boxes"), R, bev, i3d, H.stream_ptr())
+    return bev, i3d
+
+
+def eval_match_levels(iou_bev, iou_3d, keep, count, ref_boxes, levels, flags, thresholds):
+    """(tpmask, igmask) int32 [2,n] (the bits of uint32 words, bit 10 d + t): per metric, difficulty and threshold the survivors are
+    true positives, ignored or neither (evalkitti.match_levels).  levels int32 [R] on the device, or None (all rows level 0)."""
+    n, R = keep.shape[0], ref_boxes.shape[0]
+    tpmask = torch.empty((2, max(n, 1)), dtype=torch.int32, device=keep.device)
+    igmask = torch.empty((2, max(n, 1)), dtype=torch.int32, device=keep.device)
+    if n == 0:
+        return tpmask[:, :0], igmask[:, :0]
+    if levels is not None and (levels.dtype != torch.int32 or levels.numel() != R):
+        raise H.DcfError("eval_match_levels: levels must be int32 [%d]" % R)
+    H.call("dcf_eval_match_levels", _chk(iou_bev, "iou_bev") if R else None, _chk(iou_3d, "iou_3d") if R else None, _chk(keep, "keep"), count, n,
+           _chk(ref_boxes, "ref_boxes") if R else None, None if levels is None else _chk(levels, "levels"), R, _chk(flags, "flags"), thresholds,
+           thresholds.shape[0], tpmask, igmask, H.stream_ptr())
+    return tpmask, igmask
+
+
+def eval_accumulate_levels(scores, tpmask, igmask, keep, count, total, ref_boxes, levels, acc_scores, acc_tpmask, acc_igmask, state):
+    """Appends (score, tpmask[2], igmask[2]) of one sample's survivors, in order, at the device cursor state[0]; state int64 [8] =
+    (cursor, counted rows seen at easy / moderate / hard, samples with total > len(scores), unused x 3).  acc_tpmask / acc_igmask are
+    int32 [2,capacity].  The cursor counts on past the capacity; nothing is written past it."""
+    n, R = scores.shape[0], ref_boxes.shape[0]
+    if levels is not None and (levels.dtype != torch.int32 or levels.numel() != R):
+        raise H.DcfError("eval_accumulate_levels: levels must be int32 [%d]" % R)
+    if tpmask.shape != (2, n) or igmask.shape != (2, n) or acc_tpmask.shape != (2, acc_scores.shape[0]) or acc_igmask.shape != acc_tpmask.shape or state.numel() != 8:
+        raise H.DcfError("eval_accumulate_levels: masks must be [2,n], accumulators [2,capacity], state int64 [8]")
+    H.call("dcf_eval_accumulate_levels", _chk(scores, "scores"), _chk(tpmask, "tpmask"), _chk(igmask, "igmask"), _chk(keep, "keep"), count, total, n,
+           _chk(ref_boxes, "ref_boxes") if R else None, None if levels is None else _chk(levels, "levels"), R, acc_scores, _chk(acc_tpmask, "acc_tpmask"),
+           _chk(acc_igmask, "acc_igmask"), acc_scores.shape[0], state, H.stream_ptr())
+
+
+def eval_ap_levels(acc_scores, acc_tpmask, acc_igmask, state, nthr):
+    """KITTI R40 average precision per (metric, difficulty, threshold) over the detections not ignored there:
+    (ap fp64 [2,3,nthr], tp int64 [2,3,nthr], ignored int64 [2,3,nthr]) on the device."""
+    cap = acc_scores.shape[0]
+    dev = acc_scores.device
+    ap = torch.zeros((2, 3, nthr), dtype=torch.float64, device=dev)
+    tp = torch.zeros((2, 3, nthr), dtype=torch.int64, device=dev)
+    ig = torch.zeros((2, 3, nthr), dtype=torch.int64, device=dev)
+    ws = torch.empty((H.lib().dcf_eval_ap_levels_workspace_bytes(cap),), dtype=torch.uint8, device=dev)
+    H.call("dcf_eval_ap_levels", _chk(acc_scores, "acc_scores"), _chk(acc_tpmask, "acc_tpmask"), _chk(acc_igmask, "acc_igmask"), _chk(state, "state"), cap, nthr,
+           ap, tp, ig, ws, H.stream_ptr())
+    return ap, tp, ig
+
+
 # ------------------------------------------------------------------ dense focal classification loss (loss_sampling: focal, DESIGN.md section 16)
 def loss_focal_workspace(B, Hh, W, device):
     """(workspace, terms [B,3]) of loss_focal for one map shape; contents free between calls on one stream."""

@@ -12,13 +12,16 @@ of the same definitions (evalgeom.py), which is also what the device kernels are
 
 RankedTest (`eval_metric: ranked`) is the evaluator the reference never built, next to the compat one:
 suppression in score order on the (x, y) bird's-eye IoU, one-to-one matching against the labels and KITTI R40 average precision,
-accumulated on the device and read once in summary().  evalrank.py is its host statement.
+accumulated on the device and read once in summary().  evalrank.py is its host statement.  With `eval_protocol: kitti` (DESIGN.md
+section 22; host statement evalkitti.py) it additionally reports bird's-eye and 3-D AP at easy / moderate / hard, with KITTI's
+ignore rules; without the key it is what it was.
 """
 import numpy as np
 import torch
 import torch.nn as nn
 
 from . import evalgeom as EG
+from . import evalkitti as EK
 from . import evalrank as ER
 from .loss import LossTotal
 
@@ -202,11 +205,23 @@ class RankedTest(Test):
     IoU threshold, KITTI R40 average precision (definitions: evalrank.py).  accumulate() enqueues one batch on the device without
     waiting for it; summary() is the one synchronisation.  CPU tensors take the numpy statement."""
 
+    def __init__(self, pre_trained_net, config):
+        if EK.protocol(config) == "kitti":                      # bad values raise here, not in the first batch
+            EK.settings(config, self.IOU_threshold)
+        super(RankedTest, self).__init__(pre_trained_net, config)
+
     def _settings(self):
         c = self.config
         thr = c.get("eval_score_threshold")
         return (float(c["score_threshold"] if thr is None else thr), float(c.get("eval_nms_iou", 0.1)),
                 int(c.get("eval_max_candidates", 4096)), int(c.get("eval_max_detections", 131072)))
+
+    def _kitti(self):
+        """The validated settings of `eval_protocol: kitti`, or None under the plain protocol."""
+        if (self.config.get("eval_protocol") or "plain") == "plain":
+            return None
+        EK.protocol(self.config)
+        return EK.settings(self.config, self.IOU_threshold)
 
     def initialize_ap(self):
         super(RankedTest, self).initialize_ap()
@@ -222,8 +237,17 @@ class RankedTest(Test):
     def _accumulators(self, device):
         cap = self._settings()[3]
         acc = getattr(self, "_acc", None)
-        if acc is None or acc["device"] != device or acc["scores"].shape[0] != cap:
-            if device.type == "cuda":
+        kitti = self._kitti() is not None
+        if acc is None or acc["device"] != device or acc["scores"].shape[0] != cap or ("igmask" in acc) != kitti:
+            if kitti and device.type == "cuda":
+                acc = {"device": device, "scores": torch.zeros(cap, dtype=torch.float32, device=device),
+                       "tpmask": torch.zeros((2, cap), dtype=torch.int32, device=device), "igmask": torch.zeros((2, cap), dtype=torch.int32, device=device),
+                       "state": torch.zeros(8, dtype=torch.int64, device=device),
+                       "thr": torch.tensor(self.IOU_threshold, dtype=torch.float64, device=device)}
+            elif kitti:
+                acc = {"device": device, "scores": np.zeros(cap, dtype=np.float32), "tpmask": np.zeros((2, cap), dtype=np.uint32),
+                       "igmask": np.zeros((2, cap), dtype=np.uint32), "state": np.zeros(8, dtype=np.int64)}
+            elif device.type == "cuda":
                 acc = {"device": device, "scores": torch.zeros(cap, dtype=torch.float32, device=device),
                        "tpmask": torch.zeros(cap, dtype=torch.int32, device=device), "state": torch.zeros(4, dtype=torch.int64, device=device),
                        "thr": torch.tensor(self.IOU_threshold, dtype=torch.float64, device=device)}
@@ -233,9 +257,13 @@ class RankedTest(Test):
             self._acc = acc
         return acc
 
-    def accumulate(self, pred, object_data):
+    def accumulate(self, pred, object_data, levels=None, dontcare=None, crt=None):
         """One batch: rank filter, then per sample suppression, matching and the append to the accumulators.  pred [B,32,h,w] fp32
-        (the model output), object_data [B,R,9] label rows.  Nothing here waits for the device."""
+        (the model output), object_data [B,R,9] label rows.  Nothing here waits for the device.
+        Under `eval_protocol: kitti` also levels [B,R] (absent: every row level 0), dontcare [B,D,4] image rectangles (absent: none) and
+        crt, per sample the [4,3] host matrix the frame is projected with (absent or None: calib.carla_crt(), FrameGeometry's default)."""
+        if self._kitti() is not None:
+            return self._accumulate_kitti(pred, object_data, levels, dontcare, crt)
         thr, nms_iou, cap, _ = self._settings()
         acc = self._accumulators(pred.device)
         self._summary = None
@@ -269,10 +297,88 @@ class RankedTest(Test):
         self._last = (boxes, scores, count, keeps)
         return boxes, count
 
+    def _accumulate_kitti(self, pred, object_data, levels, dontcare, crt):
+        """accumulate() under `eval_protocol: kitti`: per sample the flags, both IoU matrices, the 2 x 3 x 10 matchings, the append."""
+        from . import calib
+        s = self._kitti()
+        thr, nms_iou, cap, _ = self._settings()
+        acc = self._accumulators(pred.device)
+        self._summary = None
+        B = pred.shape[0]
+        H, W = int(self.config["image_height"]), int(self.config["image_width"])
+        mats = [None if (crt is None or crt[b] is None) else crt[b] for b in range(B)]
+        mats = [calib.carla_crt() if m is None else (m.detach().cpu().numpy() if isinstance(m, torch.Tensor) else m) for m in mats]
+        mats = [np.ascontiguousarray(m, dtype=np.float32).reshape(4, 3) for m in mats]
+        keeps, marks = [], []
+        if pred.is_cuda:
+            from . import ops
+            dev = pred.device
+            refs = object_data.to(device=dev, dtype=torch.float32).contiguous()
+            lv = None if levels is None else levels.to(device=dev, dtype=torch.int32).contiguous()
+            dc = None if dontcare is None else dontcare.to(device=dev, dtype=torch.float32).contiguous()
+            boxes, scores, count, total = ops.eval_rank_filter(pred.float(), thr, cap)
+            for b in range(B):
+                cnt, lvb = count[b:b + 1], None if lv is None else lv[b]
+                keep, _ = ops.eval_nms(boxes[b], "bev", nms_iou, count=cnt)
+                flags = ops.eval_det_flags(boxes[b], cnt, mats[b], None if dc is None else dc[b], H, W, s["min_height"], s["dontcare_overlap"])
+                bev, i3d = ops.eval_iou_levels(boxes[b], keep, cnt, refs[b])
+                tpm, igm = ops.eval_match_levels(bev, i3d, keep, cnt, refs[b], lvb, flags, acc["thr"])
+                ops.eval_accumulate_levels(scores[b], tpm, igm, keep, cnt, total[b:b + 1], refs[b], lvb, acc["scores"], acc["tpmask"], acc["igmask"], acc["state"])
+                keeps.append(keep)
+                marks.append((flags, tpm, igm))
+            self._last, self._last_marks = (boxes, scores, count, keeps), marks
+            return boxes, count
+        refs = object_data.detach().float().numpy()
+        lv = None if levels is None else levels.detach().numpy() if isinstance(levels, torch.Tensor) else np.asarray(levels)
+        dc = None if dontcare is None else dontcare.detach().float().numpy() if isinstance(dontcare, torch.Tensor) else np.asarray(dontcare, np.float32)
+        boxes, scores, count, total = ER.rank_filter(pred.detach().float().numpy(), thr, cap)
+        st, capd = acc["state"], acc["scores"].shape[0]
+        for b in range(B):
+            n = int(count[b])
+            lvb = None if lv is None else lv[b]
+            keep = ER.nms(boxes[b, :n], nms_iou)
+            flags = EK.det_flags(boxes[b, :n], mats[b], H, W, None if dc is None else dc[b], s)
+            bev, i3d = EK.iou_matrices(boxes[b, :n], keep, refs[b])
+            tpm, igm = EK.match_levels(keep, refs[b], lvb, bev, i3d, flags, self.IOU_threshold)
+            for i in np.nonzero(keep)[0]:
+                if st[0] < capd:
+                    acc["scores"][st[0]], acc["tpmask"][:, st[0]], acc["igmask"][:, st[0]] = scores[b, i], tpm[:, i], igm[:, i]
+                st[0] += 1                                      # keeps counting past the capacity: summary() raises
+            st[1:4] += EK.count_rows(refs[b], lvb)
+            st[4] += int(total[b] > cap)
+            keeps.append(keep)
+            marks.append((flags, tpm, igm))
+        self._last, self._last_marks = (boxes, scores, count, keeps), marks
+        return boxes, count
+
+    def _summary_kitti(self):
+        acc = getattr(self, "_acc", None)
+        thr = self.IOU_threshold
+        if acc is None or "igmask" not in acc:
+            return EK.summarize(np.zeros(0, np.float32), np.zeros((2, 0), np.uint32), np.zeros((2, 0), np.uint32), [0, 0, 0], thr)
+        if acc["device"].type == "cuda":
+            from . import ops
+            ap, tp, ig = ops.eval_ap_levels(acc["scores"], acc["tpmask"], acc["igmask"], acc["state"], len(thr))
+            state = acc["state"].cpu().tolist()
+            self._check_capacity(state[0], acc["scores"].shape[0])
+            return EK.assemble(ap.cpu().numpy(), tp.cpu().numpy(), ig.cpu().numpy(), state[0], state[1:4], thr, state[4])
+        state = acc["state"].tolist()
+        self._check_capacity(state[0], acc["scores"].shape[0])
+        return EK.summarize(acc["scores"][:state[0]], acc["tpmask"][:, :state[0]], acc["igmask"][:, :state[0]], state[1:4], thr, state[4])
+
     def summary(self):
-        """The one synchronisation: average precision per IoU threshold (KITTI R40), their mean, and the totals."""
+        """The one synchronisation: average precision per IoU threshold (KITTI R40), their mean, and the totals.  Under
+        `eval_protocol: kitti` the dictionary of evalkitti.assemble: the same per metric ("bev", "3d") and level ("easy", "moderate",
+        "hard"); num_T / num_P / num_TP_set then report the bird's-eye moderate values."""
         if self._summary is not None:
             return self._summary
+        if self._kitti() is not None:
+            out = self._summary_kitti()
+            mod = out["bev"]["moderate"]
+            self.num_P, self.num_T = out["num_P"], mod["num_T"]
+            self.num_TP_set = dict(mod["tp"])
+            self._summary = out
+            return out
         acc = getattr(self, "_acc", None)
         thr = self.IOU_threshold
         if acc is None:
@@ -327,12 +433,13 @@ class RankedTest(Test):
                 out.append((torch.from_numpy(boxes[b][sel]), torch.from_numpy(scores[b][sel])))
         return out
 
-    def get_eval_value_onestep(self, lidar_voxel, camera_image, object_data, num_ref_box, **extra):
+    def get_eval_value_onestep(self, lidar_voxel, camera_image, object_data, num_ref_box, levels=None, dontcare=None, crt=None, **extra):
+        """levels / dontcare / crt: the protocol's optional inputs (accumulate()); they do not reach the network."""
         with torch.no_grad():
             pred = self.net(lidar_voxel, camera_image, **extra)
             pred_cls, pred_reg, pred_bbox = torch.split(pred, [4, 14, 14], dim=1)
             self.loss_value = self.loss_total(object_data.to(pred.device), num_ref_box, pred_cls, pred_reg)
-            boxes, count = self.accumulate(pred, object_data)
+            boxes, count = self.accumulate(pred, object_data, levels=levels, dontcare=dontcare, crt=crt)
         value = self.loss_value.item()                          # the caller's loss value: the step's one wait, after everything is enqueued
         n = count.cpu().tolist() if isinstance(count, torch.Tensor) else count.tolist()
         cand = [boxes[b, :n[b]] if isinstance(boxes, torch.Tensor) else torch.from_numpy(boxes[b, :n[b]]) for b in range(pred.shape[0])]

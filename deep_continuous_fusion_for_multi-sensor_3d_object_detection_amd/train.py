@@ -1085,7 +1085,12 @@ def evaluate(training, tester, dataset, loader, max_batches=None):
         for n, batch in enumerate(loader, 1):
             batch.wait()
             x_lidar, geom = training.geometry_async(dataset.geometry, batch["points"], crts=batch.get("crt"), wait_event=batch.event)
-            value, _ = tester.get_eval_value_onestep(x_lidar, batch["image"], batch["bboxes"], batch["num_bboxes"], geom=geom)
+            extra = {}
+            if getattr(tester, "_kitti", None) is not None and tester._kitti() is not None:      # eval_protocol: kitti
+                crts = batch.get("crt")                                    # the matrices geometry_async projected this batch with
+                extra = dict(levels=batch.get("bbox_level"), dontcare=batch.get("dontcare"),
+                             crt=[dataset.geometry.crt if (crts is None or crts[b] is None) else crts[b] for b in range(len(batch["points"]))])
+            value, _ = tester.get_eval_value_onestep(x_lidar, batch["image"], batch["bboxes"], batch["num_bboxes"], geom=geom, **extra)
             cum += value
             if max_batches is not None and n >= max_batches:
                 break
@@ -1099,15 +1104,21 @@ def evaluate(training, tester, dataset, loader, max_batches=None):
 def make_tester(model, config):
     """test.Test (`eval_metric` absent or compat: the reference's post-processing) or test.RankedTest (`eval_metric: ranked`)."""
     from .test import RankedTest, Test
+    from . import evalkitti
     metric = config.get("eval_metric") or "compat"
     if metric not in ("compat", "ranked"):
         raise ValueError("eval_metric must be compat or ranked (got %r)" % (metric,))
+    evalkitti.protocol(config)                                             # eval_protocol: kitti needs eval_metric: ranked
     return (RankedTest if metric == "ranked" else Test)(model, config)
 
 
 def _print_ranked(tester):
     if hasattr(tester, "summary"):
         s = tester.summary()
+        if s.get("protocol") == "kitti":
+            from . import evalkitti
+            print("    " + evalkitti.report_line(s, tester._kitti()["report_iou"]))
+            return
         print("    AP (R40) %s, mAP %.4f" % ({t: round(v, 4) for t, v in s["ap"].items()}, s["map"]))
 
 

@@ -792,6 +792,43 @@ size_t dcf_eval_ap_workspace_bytes(int64_t capacity);
 int dcf_eval_ap(const float *acc_scores, const uint32_t *acc_tpmask, const int64_t *state, int64_t capacity, int nthr, double *out_ap,
                 int64_t *out_counts, void *ws, dcf_stream_t stream);
 
+/* (version 202 still: added without a new minor) KITTI-style protocol on the ranked evaluation (`eval_protocol: kitti`, DESIGN.md
+ * section 22; evalkitti.py is the host statement): difficulty levels, a third outcome (ignored) and the 3-D IoU.  Difficulty d is
+ * 0 easy, 1 moderate, 2 hard; a label row (ref row [9], last column == 1) has a level 0..3 (levels == NULL: all 0) and is COUNTED at
+ * d iff level <= d, else IGNORED.  Mask words carry bit 10 d + t for threshold t (at most 10), one word per metric m (0 bird's-eye,
+ * 1 3-D): arrays [2][n_max] or [2][capacity].  The entries above are not affected.
+ * dcf_eval_det_flags: per candidate i < *count_dev the eight corners (the bird's-eye rectangle at z - h/2 and z + h/2) through
+ *   crt_host ([4][3] fp32 ON THE HOST, read at the call: [x, y, z, 1] . C = (u d, v d, d)) in fp64, d = ((x C02 + y C12) + z C22) + C32
+ *   and likewise u d, v d; corners with d > 0 only, u clamped to [0, image_w], v to [0, image_h]; height and area of the enclosing 2-D
+ *   box (0 with no corner in front).  flags[i] bit d iff height < min_height_host[d] (three fp64 ON THE HOST); bit 3 iff area > 0 and
+ *   for one of the D rectangles of dontcare ([D][4] fp32 on the device: l, t, r, b) iw > 0, ih > 0 and iw ih / area > overlap.
+ * dcf_eval_iou_levels: iou_bev, iou_3d [n_max][R] fp64 for the survivors (keep[i] != 0, i < *count_dev) against the labelled rows,
+ *   NaN elsewhere; one clip gives both: ia / (a1 + a2 - ia) as dcf_eval_match_ranked, and with zov = the overlap of the z extents
+ *   [z - h/2, z + h/2], iv = ia zov: iv / (a1 h1 + a2 h2 - iv).
+ * dcf_eval_match_levels: per (m, d, t) independently the survivors in row order: (A) the counted row of highest IoU among those not
+ *   yet taken (ties: the lower row), a true positive iff that IoU > thresholds_dev[t] and only then is the row taken; else (B) ignored
+ *   iff an ignored row has IoU > t (never taken); else (C) ignored iff flags[i] has bit d or bit 3.  tpmask / igmask [2][n_max] are
+ *   zeroed and receive the bits.  n_max <= 4096, R <= 4096.
+ * dcf_eval_accumulate_levels: appends (score, tpmask[2], igmask[2]) of the survivors at state[0] of acc_scores [capacity],
+ *   acc_tpmask / acc_igmask [2][capacity]; state (int64 [8], on the device) = {cursor, counted rows seen at d = 0, 1, 2, samples with
+ *   total > n_max, unused x 3}.  The cursor keeps counting past capacity; nothing is written past it.
+ * dcf_eval_ap_levels: dcf_eval_ap per (m, d, t), at index (3 m + d) nthr + t, over the detections NOT ignored there (k counts those
+ *   that stay) and n_gt = state[1 + d]: out_ap, out_tp = true positives, out_ignored = detections ignored.
+ *   ws: dcf_eval_ap_levels_workspace_bytes(capacity). */
+int dcf_eval_det_flags(const float *boxes, const int32_t *count_dev, int n_max, const float *crt_host, const float *dontcare, int D, int image_h,
+                       int image_w, const double *min_height_host, double overlap, uint32_t *flags, dcf_stream_t stream);
+int dcf_eval_iou_levels(const float *boxes, const int32_t *keep, const int32_t *count_dev, int n_max, const float *ref_boxes, int R, double *iou_bev,
+                        double *iou_3d, dcf_stream_t stream);
+int dcf_eval_match_levels(const double *iou_bev, const double *iou_3d, const int32_t *keep, const int32_t *count_dev, int n_max, const float *ref_boxes,
+                          const int32_t *levels, int R, const uint32_t *flags, const double *thresholds_dev, int nthr, uint32_t *tpmask,
+                          uint32_t *igmask, dcf_stream_t stream);
+int dcf_eval_accumulate_levels(const float *scores, const uint32_t *tpmask, const uint32_t *igmask, const int32_t *keep, const int32_t *count_dev,
+                               const int32_t *total_dev, int n_max, const float *ref_boxes, const int32_t *levels, int R, float *acc_scores,
+                               uint32_t *acc_tpmask, uint32_t *acc_igmask, int64_t capacity, int64_t *state, dcf_stream_t stream);
+size_t dcf_eval_ap_levels_workspace_bytes(int64_t capacity);
+int dcf_eval_ap_levels(const float *acc_scores, const uint32_t *acc_tpmask, const uint32_t *acc_igmask, const int64_t *state, int64_t capacity, int nthr,
+                       double *out_ap, int64_t *out_tp, int64_t *out_ignored, void *ws, dcf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
