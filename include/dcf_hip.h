@@ -499,6 +499,10 @@ int dcf_adam_step(float *params, const float *grads, float *m, float *v, int64_t
  *                                     (max_norm > 0; <= 0 = no clipping); dynamic != 0: GradScaler's rule (back off on found_inf,
  *                                     grow after growth_interval clean steps); static: the scale stays
  *   dcf_adam_step_guarded(...)       dcf_adam_step's arithmetic with the state's scalars; stores nothing when found_inf is set
+ * Edges (tests/test_gpu_optim_edges.py): the partial sums of g^2 are fp32, so finite gradients whose squares overflow give an infinite
+ * grad_norm -- while clipping that skips the step (found_inf = 1), without clipping the step is applied with clip_coef 1; a growth
+ * that would overflow float leaves the scale and resets the tracker; a skipped step leaves applied_steps, gscale, lr_over_bc1 and
+ * inv_sqrt_bc2 as they were; n == 0 gives grad_norm 0 and clip_coef 1.
  * grads must be 16-byte aligned. */
 #define DCF_AMP_PARTS 1024
 typedef struct dcf_amp_state {
@@ -529,6 +533,8 @@ int dcf_adam_step_guarded(float *params, const float *grads, float *m, float *v,
  * decay_bits: one bit per float4 group -- group j is elements 4j .. 4j+3, its bit is bit j % 64 of word j / 64 (ceil(ceil(n/4)/64)
  * words; a tail group of fewer than four elements uses its bit like any other); NULL = every element decays.
  * With decay_mul == 1, ema == NULL the stores are bit for bit dcf_adam_step's (state == NULL) / dcf_adam_step_guarded's.
+ * The products are formed left to right ((1-b2)*gk)*gk, (lr_over_bc1*m') / (...); denormals are kept, the divide and the square root
+ * are IEEE's, and nothing is clamped: with eps == 0 an element with v' == 0 gets 0 / 0 = NaN (m' == 0) or -+inf, in all three kernels.
  * params, grads, m, v, ema 16-byte aligned, decay_bits 8-byte aligned; ema must not overlap the other four; ema_omd in [0, 1].
  * A learning-rate schedule needs no entry of its own: the step's rate is passed by value here, to dcf_adam_step and to dcf_amp_update. */
 int dcf_adamw_ema_step(float *params, const float *grads, float *m, float *v, float *ema, const uint64_t *decay_bits, int64_t n,
