@@ -45,6 +45,7 @@ SIGNATURES = {
     "dcf_augment_image_batch": (c_int, [P, c_int, c_int, c_int, P, P, P]),
     "dcf_paste_points_batch": (c_int, [P, P, c_int, P, P, P, P, c_i64, P, P, P, P, c_size_t, P]),
     "dcf_paste_patches_batch": (c_int, [P, c_int, c_int, c_int, P, P, P, c_i64, P, P, P, c_size_t, P]),
+    "dcf_camera_mask_points_batch": (c_int, [P, P, c_int, P, P, c_float, c_float, c_int, c_int, P, P, P, P]),
     "dcf_knn_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dcf_knn_bev": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, P, P, P]),
     "dcf_knn_bev_batch": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float, P, P, c_size_t, P]),

@@ -12,17 +12,11 @@
 // product/sum rounds exactly where the reference's CPU arithmetic rounds.
 #include <stdlib.h>
 #include "dcf_common.h"
+#include "proj_pred.h"
 
 namespace {
 
-struct Lim6 { float v[6]; };
 struct Aff6 { float v[6]; };
-struct Crt12 { float v[12]; };
-
-__device__ __forceinline__ bool in_range(float x, float y, float z, const Lim6 &l)
-{
-    return x > l.v[0] && x < l.v[1] && y > l.v[2] && y < l.v[3] && z > l.v[4] && z < l.v[5];
-}
 
 // ------------------------------------------------------------------------------
 // Order-preserving compaction: count -> scan -> scatter.  1024 items per block.
@@ -65,33 +59,7 @@ struct RangePred {
     }
 };
 
-// data_import_carla.py:196-205 on top of the range filter of :215-226
-struct ProjPred {
-    Lim6 lim;
-    Crt12 c;
-    float ulim, vlim;
-    int mode;
-    __device__ bool operator()(const float *pts, int i, float *u, float *v) const
-    {
-        const float x = pts[3 * i], y = pts[3 * i + 1], z = pts[3 * i + 2];
-        if (!in_range(x, y, z, lim)) return false;
-        float a[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            float t = __fmul_rn(x, c.v[j]);       // the reference's K=4 sgemm chain
-            t = __fmaf_rn(y, c.v[3 + j], t);
-            t = __fmaf_rn(z, c.v[6 + j], t);
-            t = __fmaf_rn(1.0f, c.v[9 + j], t);
-            a[j] = t;
-        }
-        const float uu = __fdiv_rn(a[0], a[2]), vv = __fdiv_rn(a[1], a[2]);
-        *u = uu;
-        *v = vv;
-        bool keep = uu > 0.0f && uu < ulim && vv > 0.0f && vv < vlim;
-        if (mode == DCF_PROJ_CORRECT) keep = keep && a[2] > 0.0f;
-        return keep;
-    }
-};
+// ProjPred (data_import_carla.py:196-205 on top of the range filter of :215-226), Lim6, Crt12 and in_range: proj_pred.h
 
 template <class Pred>
 __global__ void __launch_bounds__(CP_THREADS) k_compact_count(const float *pts, int n, Pred pred, int *blocksum)

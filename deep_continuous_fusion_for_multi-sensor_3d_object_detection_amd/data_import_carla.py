@@ -117,6 +117,21 @@ class FrameGeometry(object):
                                                  getattr(self, "_proj_ws", None))
         return True
 
+    def mask_points(self, points_list, crts, fov, occluders=None, out=None):
+        """The camera visibility mask (visibility.py) of the frames of a batch, the one place that calls
+        ops.camera_mask_points_batch: with this geometry's range, limits() and projection mode, every frame under its OWN matrix
+        (crts[b], None = this geometry's).  fov: rows the projection would not keep become +inf rows; occluders: per frame None or
+        fp32 [m,5] (visibility.occluders).  out: B device tensors to write into -- out[b] may be the frame itself (in place);
+        None = new tensors: the frames handed in are never written.  Returns the B masked frames [n_b,3]."""
+        pts = [self._pts(p) for p in points_list]
+        if out is None:
+            out = [torch.empty_like(p) for p in pts]
+        ulim, vlim = self.limits()
+        mats = np.stack([np.ascontiguousarray(self.crt if (crts is None or crts[b] is None) else crts[b], dtype=np.float32).reshape(12)
+                         for b in range(len(pts))], 0)
+        ops.camera_mask_points_batch(pts, mats, self.grid.lim, ulim, vlim, self.proj_mode, fov, occluders, list(out))
+        return [o[:p.shape[0]] for o, p in zip(out, pts)]
+
     def __call__(self, lidar_points, want_ids=False, voxel_out=None, voxel_mode=None):
         """lidar_points [N,3] f32 (any device) -> (voxel [Cz,L,W], pointcloud_raw [max_num_pc,3],
         uv [max_num_pc,2], n_valid int32[1] on device, ids or None).  voxel_out: optional [Cz,L,W] slice of a
@@ -139,6 +154,9 @@ class CarlaDataset(Dataset):
         self.raw = bool(raw)
         self.want_bev_image = bool(want_bev_image)
         self._geometry = None
+        # `camera_mask.fov_crop`: a non-raw item masks its points as the trainer's geometry does
+        from . import visibility
+        self._fov_crop = bool((visibility.parse_config(config) or {}).get("fov_crop", False))
         self.CRT_tensor = torch.from_numpy(calib.carla_crt())
         self._pid = None
         self.hdf5_files = self.load_dataset(mode)
@@ -220,6 +238,8 @@ class CarlaDataset(Dataset):
 
     def Voxelization_Projection(self, lidar_data, interpolate=True):
         """interpolate=False: occupancy grid (the voxel of the trunc'd ids := 1, data_import_carla.py:231-234)."""
+        if self._fov_crop:
+            lidar_data = self.geometry.mask_points([lidar_data], None, True)[0]
         voxel, pc, uv, cnt, ids = self.geometry(lidar_data, want_ids=self.want_bev_image,
                                                 voxel_mode=None if interpolate else H.VOXEL_OCCUPANCY)
         return voxel, pc, uv, cnt, ids

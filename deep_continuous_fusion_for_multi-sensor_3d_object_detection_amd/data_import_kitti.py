@@ -154,6 +154,9 @@ class KittiDataset(Dataset):
             from . import evalkitti as EK
             EK.protocol(config)
             self._protocol = EK.settings(config)
+        # `camera_mask.fov_crop`: a non-raw item masks its points as the trainer's geometry does
+        from . import visibility
+        self._fov_crop = bool((visibility.parse_config(config) or {}).get("fov_crop", False))
 
     def __len__(self):
         return len(self.ids)
@@ -194,6 +197,8 @@ class KittiDataset(Dataset):
         if self.raw:
             return dict({"image": image, "bboxes": boxes, "num_bboxes": n, "lidar_points": pts, "crt": crt}, **extra)
         g = self.geometry
+        if self._fov_crop:
+            pts = g.mask_points([pts], [crt.numpy()], True)[0]
         voxel = g.voxelize(pts)
         pc, uv, cnt = g.project(pts, crt=crt.numpy())
         sample = {"image": image, "bboxes": boxes, "num_bboxes": n, "pointcloud_raw": pc, "projected_loc_uv": uv,

@@ -488,6 +488,46 @@ def augment_points_batch(pts_list, params, out_list=None):
     return out_list
 
 
+def camera_mask_points_batch(pts_list, crts, lim, ulim, vlim, mode, fov, occ_list=None, out_list=None):
+    """The camera visibility mask (visibility.py) of the frames of a batch: pts_list = B device tensors [n_b,3]
+    fp32 (views at any point offset of a larger buffer included), crts [B,4,3] (or [B,12]) host floats, one matrix per frame; lim,
+    ulim, vlim, mode as for project_filter_batch; fov: rows the projection would not keep become +inf rows; occ_list: per frame None
+    or fp32 [m_b,5] = (x0, y0, x1, y1, D), m_b <= 16 (visibility.occluders); out_list: B tensors to write into (None = in place).
+    Bit for bit visibility.mask_points per frame.  One launch per 8 frames.  Returns out_list."""
+    B = len(pts_list)
+    if (out_list is not None and len(out_list) != B) or (occ_list is not None and len(occ_list) != B):
+        raise H.DcfError("camera_mask_points_batch: %d frames, %s outputs, %s occluder sets"
+                         % (B, "no" if out_list is None else len(out_list), "no" if occ_list is None else len(occ_list)))
+    out_list = pts_list if out_list is None else out_list
+    for p, o in zip(pts_list, out_list):
+        for t in (p, o):
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
+                raise H.DcfError("camera_mask_points_batch: frames must be contiguous fp32 CUDA tensors")
+        if o.numel() < p.numel():
+            raise H.DcfError("camera_mask_points_batch: output smaller than its frame")
+    crt = np.ascontiguousarray(np.asarray(crts, dtype=np.float32).reshape(B, 12))
+    for b0 in range(0, B, 8):
+        sl = slice(b0, min(b0 + 8, B))
+        k = sl.stop - sl.start
+        occ = np.zeros((k, 16, 5), dtype=np.float32)
+        ms = (ctypes.c_int * k)()
+        for i in range(k):
+            q = None if occ_list is None else occ_list[b0 + i]
+            if q is None:
+                continue
+            q = np.asarray(q, dtype=np.float32).reshape(-1, 5)
+            if len(q) > 16:
+                raise H.DcfError("camera_mask_points_batch: a frame holds at most 16 occluders (got %d)" % len(q))
+            ms[i] = len(q)
+            occ[i, :len(q)] = q
+        ptrs = (ctypes.c_void_p * k)(*[p.data_ptr() if p.shape[0] else None for p in pts_list[sl]])
+        outs = (ctypes.c_void_p * k)(*[o.data_ptr() if p.shape[0] else None for p, o in zip(pts_list[sl], out_list[sl])])
+        ns = (ctypes.c_int * k)(*[int(p.shape[0]) for p in pts_list[sl]])
+        H.call("dcf_camera_mask_points_batch", ctypes.addressof(ptrs), ctypes.addressof(ns), k, H.host_f32(lim), np.ascontiguousarray(crt[sl]),
+               float(ulim), float(vlim), int(mode), int(bool(fov)), ctypes.addressof(ms), occ, ctypes.addressof(outs), H.stream_ptr())
+    return out_list
+
+
 def augment_image_batch(img_u8, params, out=None):
     """Train-time camera image augmentation (augment_image.py) of the frames of a batch: img_u8 = a contiguous
     uint8 device tensor [B,3,H,W] (a view at any byte offset of a larger buffer included), params = B augment_image.draw results;

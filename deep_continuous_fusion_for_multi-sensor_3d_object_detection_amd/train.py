@@ -253,10 +253,25 @@ def parse_paste_config(config):
     return out
 
 
-def draw_paste_plans(cfg, bank, rank, call, boxes, nums, n_points, crts, config):
+def parse_camera_mask_config(config):
+    """The `camera_mask` block (visibility.py): None = off (no block, or both switches false: no buffer, no
+    launch), else {"fov_crop", "paste_occlusion"}.  Unknown keys and non-boolean values raise ValueError, and so does
+    paste_occlusion: true without an enabled augment_paste block with paste_image: true -- the occluders are the painted patches."""
+    from . import visibility as VIS
+    out = VIS.parse_config(config)
+    if out is not None and out["paste_occlusion"]:
+        pst = parse_paste_config(config)
+        if pst is None or not pst["paste_image"]:
+            raise ValueError("camera_mask.paste_occlusion needs an enabled augment_paste block with paste_image: true")
+    return out
+
+
+def draw_paste_plans(cfg, bank, rank, call, boxes, nums, n_points, crts, config, dropped=None):
     """The per-frame plans of one step (paste.draw) and the labels with the pasted rows behind the frame's own, all on the host:
     (plans, boxes' float32 [B, max_num_bbox, 9], nums' [B]).  cfg None (block absent or disabled): empty plans, the labels as
-    they came."""
+    they came.  dropped (camera_mask.paste_occlusion): a list; every plan then goes through visibility.drop_covering before its labels
+    are appended -- a candidate whose patch would be painted over a nearer label of the frame is not pasted -- and the list
+    receives the number of objects each frame lost."""
     from . import paste as PST
     src = np.asarray(boxes, dtype=np.float32)
     cnt = [int(v) for v in np.asarray(nums).reshape(-1)]
@@ -264,6 +279,11 @@ def draw_paste_plans(cfg, bank, rank, call, boxes, nums, n_points, crts, config)
     if cfg is None:
         return [PST.empty_plan(n_points[b], hw) for b in range(len(cnt))], src, cnt
     plans = [PST.draw(cfg, cfg["seed"], rank, call, b, bank, src[b], cnt[b], n_points[b], crts[b], config) for b in range(len(cnt))]
+    if dropped is not None:
+        from . import visibility as VIS
+        drawn = plans
+        plans = [VIS.drop_covering(drawn[b], src[b], cnt[b], crts[b], bank) for b in range(len(cnt))]
+        dropped.extend(len(d["rows"]) - len(p["rows"]) for d, p in zip(drawn, plans))
     moved = [PST.append_labels(src[b], cnt[b], plans[b]) for b in range(len(cnt))]
     return plans, np.stack([m[0] for m in moved], 0), [m[1] for m in moved]
 
@@ -471,6 +491,11 @@ class Train(nn.Module):
             PST.check_bank(self._paste_bank, (config["image_height"], config["image_width"]) if self.paste["paste_image"] else None)
             dev = self.model.flat_params.device
             self._paste_dev = (torch.from_numpy(self._paste_bank["points"]).to(dev), torch.from_numpy(self._paste_bank["patch"]).to(dev))
+        # the camera visibility mask (visibility.py; None = off, the default: no buffer, no launch).  fov_crop acts wherever
+        # geometry_async runs (train and evaluation), paste_occlusion where pasting does; last_masked = per frame of the last
+        # paste step (patch records that act as occluders, objects dropped by visibility.drop_covering), host counts for logs
+        self.camera_mask = parse_camera_mask_config(config)
+        self.last_masked = []
         # the accumulator of gradient accumulation: allocated only when a window holds more than one micro-step
         self.accum_buf = torch.empty_like(self.model.flat_grads.detach()) if self.accum is not None else None
         self._accum_index = 0
@@ -583,6 +608,8 @@ class Train(nn.Module):
                 else:
                     dst = [torch.empty((r, 3), dtype=torch.float32, device=src[0].device) for r in rows]
                 points_list = ops.paste_points_batch(src, list(paste), self._paste_dev[0], dst)
+            if self.camera_mask is not None:
+                points_list = self._camera_mask_points(frame_geometry, points_list, crts, paste, st, mp)
             if augment is not None:
                 from . import augment as AUG
                 if len(augment) != Bn:
@@ -662,6 +689,33 @@ class Train(nn.Module):
                 if t is not None:
                     t.record_stream(main)
         return x_lidar, geom
+
+    def _camera_mask_points(self, frame_geometry, points_list, crts, paste, st, mp):
+        """The camera visibility mask of geometry_async, on the side stream behind the paste launch and in
+        front of `augment`: every frame under its OWN, un-augmented matrix -- augment.compose_crt keeps every point on the pixel of
+        its original, so the decision holds under the BEV and image blocks.  Pasted frames (buffers of this call) are masked in
+        place; the loader's staging views are never written: their masked copy goes to a persistent [B, max_num_pc, 3] buffer of
+        the geometry set, or -- a frame over max_num_pc, as for `augment` -- to new tensors."""
+        from . import visibility as VIS
+        cm, Bn = self.camera_mask, len(points_list)
+        own = [frame_geometry.crt if (crts is None or crts[b] is None) else crts[b] for b in range(Bn)]
+        occ = None
+        if cm["paste_occlusion"] and paste is not None:
+            occ = [VIS.occluders(paste[b], self._paste_bank, own[b]) for b in range(Bn)]
+            if not any(len(q) for q in occ):
+                occ = None
+        if not cm["fov_crop"] and occ is None:
+            return points_list
+        src = [frame_geometry._pts(p) for p in points_list]
+        if paste is not None:
+            dst = src
+        elif st is not None:
+            if "mask" not in st:
+                st["mask"] = torch.empty((Bn, mp, 3), dtype=torch.float32, device=src[0].device)
+            dst = [st["mask"][b, :p.shape[0]] for b, p in enumerate(src)]
+        else:
+            dst = None
+        return frame_geometry.mask_points(src, own, cm["fov_crop"], occ, out=dst)
 
     def _predict(self, lidar_voxel, camera_image, extra):
         pred = self.model(lidar_voxel, camera_image, **extra)
@@ -825,9 +879,12 @@ class Train(nn.Module):
         rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
         points, crts = batch["points"], batch.get("crt")
         own = [frame_geometry.crt if (crts is None or crts[b] is None) else crts[b] for b in range(len(points))]
+        dropped = [] if (self.camera_mask is not None and self.camera_mask["paste_occlusion"]) else None
         plans, new_boxes, new_nums = draw_paste_plans(self.paste, self._paste_bank, rank, call, boxes.detach().cpu().numpy(), torch.as_tensor(nums).numpy(),
-                                                      [int(p.shape[0]) for p in points], own, frame_geometry.config)
+                                                      [int(p.shape[0]) for p in points], own, frame_geometry.config, dropped=dropped)
         self.last_paste = [list(p["rows"]) for p in plans]
+        if dropped is not None:
+            self.last_masked = [(len(p["patches"]), d) for p, d in zip(plans, dropped)]
         boxes = torch.from_numpy(new_boxes).to(boxes.dtype)
         nums = torch.tensor(new_nums, dtype=torch.as_tensor(nums).dtype)
         if self.augment is not None:               # (draws at aug_calls == call and counts it)
@@ -1156,11 +1213,14 @@ def main():
             print("epoch %d: learning rate %.6g" % (epoch, training.learning_rate()))
         terms_sum, terms_n = None, 0                                       # focal: the epoch's mean terms, added up on the device
         pasted, pasted_frames = 0, 0                                       # augment_paste: accepted objects / frames of the epoch
+        occluders, covering = 0, 0                                         # camera_mask.paste_occlusion: occluding patches / dropped objects
         for batch_ndx, batch in enumerate(loader):
             training.one_step_raw(dataset.geometry, batch)
             if training.paste is not None:
                 pasted += sum(len(rows) for rows in training.last_paste)
                 pasted_frames += len(training.last_paste)
+                occluders += sum(m for m, _ in training.last_masked)
+                covering += sum(d for _, d in training.last_masked)
             terms = training.loss_terms()
             if terms is not None:                                          # (the batch mean is over the samples the reduction counts)
                 counted = terms[-1:] if training.loss_total.reduction == "last" else terms
@@ -1182,6 +1242,9 @@ def main():
         #                                                                    evaluation below and the next save see no open window
         if rank0 and pasted_frames:
             print("epoch %d: %.2f pasted objects per frame (%d frames)" % (epoch, pasted / pasted_frames, pasted_frames))
+            if training.camera_mask is not None and training.camera_mask["paste_occlusion"]:
+                print("epoch %d: camera mask: %.2f occluding patches and %.2f objects dropped over nearer labels per frame"
+                      % (epoch, occluders / pasted_frames, covering / pasted_frames))
         if rank0 and terms_n:
             cls_mean, reg_mean, npos_mean = (terms_sum / terms_n).tolist()
             what = "positive anchors" if training.loss_total.sampling == "anchor" else "positive cells"

@@ -99,6 +99,20 @@ int dcf_project_filter(const float *pts, int n, const float *lim, const float *c
 int dcf_project_filter_batch(const float *const *pts, const int *n, int B, const float *lim, const float *crt, float ulim, float vlim,
                              int mode, float *uv_out, float *xyz_out, int rows, int32_t *count_dev, void *ws, dcf_stream_t stream);
 
+/* The camera visibility mask for the B (<= 8) frames of a batch in one launch (host statement: visibility.py).
+ * HOST arrays: pts / out B device pointers to [n[b]][3] points (4-byte alignment is all that is assumed; out[b] == pts[b] is
+ * allowed, any other overlap is refused), n B row counts (0 is legal), crt float[B][12] one projection matrix per frame, m B occluder
+ * counts (<= 16), occ float[B][16][5] = {x0, y0, x1, y1, D} (finite, x1 >= x0, y1 >= y0: refused otherwise; may be NULL when every
+ * m[b] is 0); lim float[6], ulim, vlim, mode as in dcf_project_filter.  With (u, v, a2) the projection's own fp32 chain
+ *   a_j = fma(1, c[3][j], fma(z, c[2][j], fma(y, c[1][j], fl(x c[0][j]))))   u = fl(a0 / a2)   v = fl(a1 / a2)
+ * row i of frame b is written as (+inf, +inf, +inf) iff
+ *   (fov != 0 and the row fails dcf_project_filter's keep predicate) or
+ *   (for some occluder j < m[b]:  u >= x0 && u < x1 && v >= y0 && v < y1 && a2 > D)        (a NaN compares false)
+ * and is copied bit for bit otherwise (a NaN keeps its payload).  Every range test of this library rejects a +inf row: nothing is
+ * compacted, the point counts do not change.  Nothing is written beyond row n[b].  The tables travel in the kernel argument. */
+int dcf_camera_mask_points_batch(const float *const *pts, const int *n, int B, const float *lim, const float *crt, float ulim, float vlim,
+                                 int mode, int fov, const int *m, const float *occ, float *const *out, dcf_stream_t stream);
+
 /* Train-time BEV augmentation of the B (<= 8) frames of a batch in one launch (host statement: augment.py).
  * pts / out: HOST arrays of B device pointers to [n[b]][3] points (4-byte alignment is all that is assumed; out[b] == pts[b] is
  * allowed, any other overlap is refused); n HOST int[B] (0 is legal); mat HOST float[B][5] = {a00, a01, a10, a11, a22} of
