@@ -54,6 +54,7 @@ SIGNATURES = {
     "dcf_nchw_to_nhwc": (c_int, [c_int, P, P, c_int, c_int, c_int, c_int, P]),
     "dcf_nhwc_to_nchw": (c_int, [c_int, P, P, c_int, c_int, c_int, c_int, P]),
     "dcf_image_to_nhwc4": (c_int, [c_int, P, P, c_int, c_int, c_int, P]),
+    "dcf_image_to_nhwc4_norm": (c_int, [c_int, P, P, c_int, c_int, c_int, P, P, P]),
     "dcf_conv2d_fwd": (c_int, [c_int, P, P, P, P, P] + [c_int] * 12 + [P]),
     "dcf_conv2d_fwd_rowscale": (c_int, [c_int, P, P, P, P, P, P] + [c_int] * 12 + [P]),
     "dcf_conv2d_dgrad": (c_int, [c_int, P, P, P, P, P] + [c_int] * 11 + [P]),
@@ -168,6 +169,8 @@ SIGNATURES = {
     "dcf_adam_step_guarded": (c_int, [P, P, P, P, c_i64, c_float, c_float, c_float, P, P]),
     # training recipe: AdamW decay + weight EMA in the Adam pass (csrc/optim.hip)
     "dcf_adamw_ema_step": (c_int, [P, P, P, P, P, P, c_i64, c_float, c_float, c_float, c_float, c_int, c_float, c_float, c_float, P, P]),
+    # param_groups: the same pass with a per-float4 group id and {mu, decay_mul, frozen} per id (csrc/optim.hip)
+    "dcf_adamw_ema_step_groups": (c_int, [P, P, P, P, P, P, P, c_int, P, c_i64, c_float, c_float, c_float, c_float, c_int, c_float, c_float, P, P]),
     # gradient accumulation: dst = src / dst += src on the arena or a range of it (csrc/optim.hip)
     "dcf_grad_accumulate": (c_int, [P, P, c_i64, c_int, P]),
 }
@@ -242,6 +245,14 @@ class AmpState(ctypes.Structure):
                 ("applied_steps", c_i64), ("skipped_steps", c_i64), ("grad_norm", c_float), ("clip_coef", c_float),
                 ("gscale", c_float), ("lr_over_bc1", c_float), ("inv_sqrt_bc2", c_float), ("pad_", ctypes.c_int32 * 3),
                 ("part_sum", c_float * AMP_PARTS), ("part_flag", ctypes.c_int32 * AMP_PARTS)]
+
+
+ADAM_MAX_GROUPS = 16         # DCF_ADAM_MAX_GROUPS
+
+
+class AdamGroup(ctypes.Structure):
+    """struct dcf_adam_group of include/dcf_hip.h."""
+    _fields_ = [("mu", c_float), ("decay_mul", c_float), ("frozen", ctypes.c_int32)]
 
 
 class DcfError(RuntimeError):

@@ -174,9 +174,10 @@ class HipBackend(object):
             hit = cache.get(sig)
             if hit is None:
                 off = goff = 0
+                fz = self.frozen_rows
                 for L in layers:
-                    if L.out_shape is None:
-                        L.nsplit, L.slab_off, L.gsum_off = 0, 0, 0
+                    if L.out_shape is None or (fz is not None and fz[0] <= L.idx < fz[1]):
+                        L.nsplit, L.slab_off, L.gsum_off = 0, 0, 0       # (a frozen row: no weight gradient is queued, no slab is read)
                         continue
                     B, Ho, Wo = L.out_shape
                     L.nsplit = ops.conv2d_wgrad_splits(B, Ho, Wo, L.cin, L.cout_pad, L.kh, L.kw, L.stride)
@@ -245,7 +246,29 @@ class HipBackend(object):
             return [(min(l4), f0)] if l4 else None
         raise ValueError("unknown gradient bucket %r" % (which,))
 
+    # Frozen trunk prefix: (lo, hi), one run of layer-table rows whose parameters a frozen parameter group
+    # holds and whose backward the plan skips (engine.Plan.set_frozen_trunk), or None.  Those rows are never finalised -- no slab of
+    # theirs exists or is read -- and their range of the gradient arena keeps the exact zeros it was allocated with.
+    frozen_rows = None
+
+    def set_frozen_rows(self, rows):
+        rows = None if rows is None else (int(rows[0]), int(rows[1]))
+        if rows != self.frozen_rows:
+            self.frozen_rows = rows
+            self._sig = None                           # the slab plan changes: frozen rows get no slabs
+            self.__dict__.pop("_bw_cache", None)
+
     def _finalize(self, lo, hi):
+        fz = self.frozen_rows
+        if fz is not None and lo < fz[1] and fz[0] < hi:
+            if lo < fz[0]:
+                self._finalize_rows(lo, fz[0])
+            if fz[1] < hi:
+                self._finalize_rows(fz[1], hi)
+            return
+        self._finalize_rows(lo, hi)
+
+    def _finalize_rows(self, lo, hi):
         tab = self.table.data_ptr() + lo * ctypes.sizeof(H.ConvParam)
         H.call("dcf_wgrad_finalize_rows", tab, hi - lo, ctypes.addressof(self._couts) + 4 * lo, self.params, self.buffers, self.ssarena,
                self.slabs, self.gsum, self.grads, BN_EPS, H.stream_ptr())
@@ -658,6 +681,11 @@ class HipBackend(object):
         if img.dtype != torch.uint8:
             raise H.DcfError("x_image must be uint8 [B,3,H,W] (data_import_carla.py:62)")
         return ops.image_to_nhwc4(img.contiguous(), self.dtype)
+
+    def image_to_nhwc4_norm(self, img, mean, std):
+        if img.dtype != torch.uint8:
+            raise H.DcfError("x_image must be uint8 [B,3,H,W] (data_import_carla.py:62)")
+        return ops.image_to_nhwc4_norm(img.contiguous(), self.dtype, mean, std)
 
     def resize_fwd(self, x, out_hw, align, add):
         return ops.resize_bilinear_fwd(self.dtype, x, out_hw, align, add)

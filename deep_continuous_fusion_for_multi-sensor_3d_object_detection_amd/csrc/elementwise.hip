@@ -5,6 +5,7 @@
 //
 // All activations are NHWC; every kernel moves 8-16 B per lane and is priced against the
 // HBM roofline.  Reference lines are cited per kernel.
+#include <math.h>
 #include <stdlib.h>
 
 #include "dcf_common.h"
@@ -70,6 +71,37 @@ __global__ void __launch_bounds__(256) k_image_to_nhwc4(const uint8_t *img, T *y
         v.x = (float)s[0] / 255.0f;
         v.y = (float)s[HW] / 255.0f;
         v.z = (float)s[2 * HW] / 255.0f;
+    }
+    st4(y + p * 4, v);
+}
+
+// k_image_to_nhwc4 with the input normalisation of `fusion.image_norm`: per plane c of the input's own
+// order, v = ((float)s / 255 - mean[c]) / std[c] -- three correctly rounded fp32 operations, spelled with __fdiv_rn / __fsub_rn
+// like the geometry chains (nothing contracted, no reciprocal formed).  Halo pixels and channel 3 stay +0: the stem's zero halo
+// stands for NORMALISED zero, which is why the tables cannot be folded into the stem weights.  Same layout, same launch shape;
+// with mean = 0 and std = 1 every stored bit is k_image_to_nhwc4's (x - 0 = x, x / 1 = x).
+struct ImageNorm {
+    float mean[3], std[3];
+};
+
+template <typename T>
+__global__ void __launch_bounds__(256) k_image_to_nhwc4_norm(const uint8_t *img, T *y, int B, int H, int W, ImageNorm nm)
+{
+    const int Hp = H + 6, Wp = W + 8;
+    const int64_t total = (int64_t)B * Hp * Wp;
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= total) return;
+    const int b = (int)(p / ((int64_t)Hp * Wp));
+    const int rem = (int)(p - (int64_t)b * Hp * Wp);
+    const int hp = rem / Wp, wp = rem - hp * Wp;
+    const int h = hp - 3, w = wp - 3;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (h >= 0 && h < H && w >= 0 && w < W) {
+        const int64_t HW = (int64_t)H * W;
+        const uint8_t *s = img + (int64_t)b * 3 * HW + (int64_t)h * W + w;
+        v.x = __fdiv_rn(__fsub_rn(__fdiv_rn((float)s[0], 255.0f), nm.mean[0]), nm.std[0]);
+        v.y = __fdiv_rn(__fsub_rn(__fdiv_rn((float)s[HW], 255.0f), nm.mean[1]), nm.std[1]);
+        v.z = __fdiv_rn(__fsub_rn(__fdiv_rn((float)s[2 * HW], 255.0f), nm.mean[2]), nm.std[2]);
     }
     st4(y + p * 4, v);
 }
@@ -1208,6 +1240,24 @@ extern "C" int dcf_image_to_nhwc4(int dtype, const uint8_t *img, void *y, int B,
     const int64_t total = (int64_t)B * (H + 6) * (W + 8);
     hipStream_t s = S(stream);
     DCF_DISPATCH_DTYPE(dtype, { DCF_LAUNCH_B("image_to_nhwc4", (double)B * H * W * 3 + (double)total * 4 * sizeof(T), s, hipLaunchKernelGGL(k_image_to_nhwc4<T>, dim3(cdiv(total, 256)), dim3(256), 0, s, img, (T *)y, B, H, W)); })
+    return DCF_OK;
+}
+
+extern "C" int dcf_image_to_nhwc4_norm(int dtype, const uint8_t *img, void *y, int B, int H, int W, const float *mean, const float *std,
+                                       dcf_stream_t stream)
+{
+    DCF_REQUIRE(img && y && mean && std, "dcf_image_to_nhwc4_norm: null pointer");
+    ImageNorm nm;
+    for (int c = 0; c < 3; ++c) {
+        DCF_REQUIRE(isfinite(mean[c]) && isfinite(std[c]) && std[c] > 0.f,
+                    "dcf_image_to_nhwc4_norm: mean must be finite and std finite and greater than 0 (plane %d: mean %g, std %g)", c,
+                    (double)mean[c], (double)std[c]);
+        nm.mean[c] = mean[c];
+        nm.std[c] = std[c];
+    }
+    const int64_t total = (int64_t)B * (H + 6) * (W + 8);
+    hipStream_t s = S(stream);
+    DCF_DISPATCH_DTYPE(dtype, { DCF_LAUNCH_B("image_to_nhwc4_norm", (double)B * H * W * 3 + (double)total * 4 * sizeof(T), s, hipLaunchKernelGGL(k_image_to_nhwc4_norm<T>, dim3(cdiv(total, 256)), dim3(256), 0, s, img, (T *)y, B, H, W, nm)); })
     return DCF_OK;
 }
 

@@ -193,6 +193,162 @@ extern "C" int dcf_adamw_ema_step(float *params, const float *grads, float *m, f
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
+// Parameter groups (`param_groups`): the pass above with a second side table, one BYTE per float4 group naming
+// the group's id g (0 .. ngroups-1), and per id {mu, decay_mul, frozen} by value in the kernel argument:
+//     frozen_g :  the float4 group is skipped -- g is not read, p, m, v, e are not stored (they keep their bits whatever g holds)
+//     else     :  update1 / average1 above with lr_over_bc1 * mu_g (one fp32 product) for lr_over_bc1 and decay_mul_g for decay_mul
+// With mu == 1 everywhere and nothing frozen the stores are dcf_adamw_ema_step's bits (x * 1 = x).  Same two launch shapes; a wave of
+// the flat shape reads 64 consecutive id bytes beside its one mask word.  An id is masked to the table's 16 entries and the entries from
+// ngroups on are marked frozen, so an id the table does not hold stores nothing (ops.AdamGroups refuses such ids where they are built).
+struct AdamGroupTable {
+    float mu[DCF_ADAM_MAX_GROUPS], decay_mul[DCF_ADAM_MAX_GROUPS];
+    uint32_t frozen;
+};
+
+namespace {
+
+__device__ __forceinline__ bool group_scalars(AdamwScalars &cg, const AdamwScalars &c, const AdamGroupTable &t, const uint8_t *ids, int64_t group)
+{
+    const int id = ids[group] & (DCF_ADAM_MAX_GROUPS - 1);
+    if ((t.frozen >> id) & 1u) return false;
+    // the table sits in scalar registers (constant indices below): 2 x 15 selects per lane instead of two loads that depend on the
+    // id load -- with the dependent loads the pass measured 2.2 us (1.8 %) over dcf_adamw_ema_step at the cfg2 arena size
+    float mu = t.mu[0], dm = t.decay_mul[0];
+#pragma unroll
+    for (int k = 1; k < DCF_ADAM_MAX_GROUPS; ++k) {
+        mu = id == k ? t.mu[k] : mu;
+        dm = id == k ? t.decay_mul[k] : dm;
+    }
+    cg = c;
+    cg.lr_over_bc1 = c.lr_over_bc1 * mu;
+    cg.decay_mul = dm;
+    return true;
+}
+
+template <bool EMA>
+__device__ __forceinline__ void ggroup1(float *p, const float *g, float *m, float *v, float *e, const uint64_t *bits, const uint8_t *ids,
+                                        int64_t n, int64_t group, const AdamwScalars &c, const AdamGroupTable &t)
+{
+    AdamwScalars cg;
+    if (group_scalars(cg, c, t, ids, group)) group1<EMA>(p, g, m, v, e, bits, n, group, cg);
+}
+
+}  // namespace
+
+template <bool GUARD, bool EMA>
+__global__ void __launch_bounds__(kThreads) k_adamw_groups_flat(float *p, const float *g, float *m, float *v, float *e, const uint64_t *bits,
+                                                                 const uint8_t *ids, int64_t n, AdamwScalars c, AdamGroupTable t,
+                                                                 const dcf_amp_state *st)
+{
+    if (!scalars<GUARD>(c, st)) return;
+    const int64_t group = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (group * 4 >= n) return;
+    ggroup1<EMA>(p, g, m, v, e, bits, ids, n, group, c, t);
+}
+
+template <bool GUARD, bool EMA>
+__global__ void __launch_bounds__(kThreads) k_adamw_groups_stride(float *p, const float *g, float *m, float *v, float *e, const uint64_t *bits,
+                                                                   const uint8_t *ids, int64_t n, AdamwScalars c, AdamGroupTable t,
+                                                                   const dcf_amp_state *st)
+{
+    if (!scalars<GUARD>(c, st)) return;
+    const int64_t whole = n >> 2;
+    const int64_t groups = (n + 3) >> 2;
+    const int64_t step = (int64_t)gridDim.x * (2 * kThreads);
+    int64_t base = (int64_t)blockIdx.x * (2 * kThreads);
+    for (; base + 2 * kThreads <= whole; base += step) {      // both of the lane's groups whole; a frozen one loads nothing
+        const int64_t ga = base + threadIdx.x, gb = ga + kThreads;
+        const int64_t ia = ga * 4, ib = gb * 4;
+        AdamwScalars ca, cb;
+        const bool la = group_scalars(ca, c, t, ids, ga), lb = group_scalars(cb, c, t, ids, gb);
+        float4 pa, ga4, ma, va, ea, pb, gb4, mb, vb, eb;
+        if (la) {
+            pa = ld4(p + ia); ga4 = ld4(g + ia); ma = ld4(m + ia); va = ld4(v + ia);
+            if (EMA) ea = ld4(e + ia);
+        }
+        if (lb) {
+            pb = ld4(p + ib); gb4 = ld4(g + ib); mb = ld4(m + ib); vb = ld4(v + ib);
+            if (EMA) eb = ld4(e + ib);
+        }
+        if (la) {
+            update4(pa, ga4, ma, va, decays(bits, ga), ca);
+            st4(p + ia, pa); st4(m + ia, ma); st4(v + ia, va);
+            if (EMA) st4(e + ia, average4(ea, pa, ca));
+        }
+        if (lb) {
+            update4(pb, gb4, mb, vb, decays(bits, gb), cb);
+            st4(p + ib, pb); st4(m + ib, mb); st4(v + ib, vb);
+            if (EMA) st4(e + ib, average4(eb, pb, cb));
+        }
+    }
+    if (base < groups) {                                  // the one chunk that is not whole (one workgroup gets here)
+        const int64_t ga = base + threadIdx.x, gb = ga + kThreads;
+        if (ga < groups) ggroup1<EMA>(p, g, m, v, e, bits, ids, n, ga, c, t);
+        if (gb < groups) ggroup1<EMA>(p, g, m, v, e, bits, ids, n, gb, c, t);
+    }
+}
+
+extern "C" int dcf_adamw_ema_step_groups(float *params, const float *grads, float *m, float *v, float *ema, const uint64_t *decay_bits,
+                                         const uint8_t *group_ids, int ngroups, const dcf_adam_group *groups, int64_t n, float lr, float beta1,
+                                         float beta2, float eps, int step, float gscale, float ema_omd, const dcf_amp_state *state,
+                                         dcf_stream_t stream)
+{
+    DCF_REQUIRE(params && grads && m && v && group_ids && groups && n >= 0 && (state || step >= 1),
+                "dcf_adamw_ema_step_groups: bad arguments (params %p, grads %p, m %p, v %p, group_ids %p, groups %p, n %lld, step %d, state %p)",
+                (void *)params, (const void *)grads, (void *)m, (void *)v, (const void *)group_ids, (const void *)groups, (long long)n, step,
+                (const void *)state);
+    DCF_REQUIRE(ngroups >= 1 && ngroups <= DCF_ADAM_MAX_GROUPS, "dcf_adamw_ema_step_groups: 1 to %d groups (got %d)", DCF_ADAM_MAX_GROUPS, ngroups);
+    DCF_REQUIRE(aligned(params, 16) && aligned(grads, 16) && aligned(m, 16) && aligned(v, 16) && aligned(ema, 16) && aligned(decay_bits, 8),
+                "dcf_adamw_ema_step_groups: params, grads, m, v, ema must be 16-byte aligned and decay_bits 8-byte aligned");
+    DCF_REQUIRE(isfinite(ema_omd) && ema_omd >= 0.f && ema_omd <= 1.f, "dcf_adamw_ema_step_groups: ema_omd must be in [0, 1] (got %g)", (double)ema_omd);
+    DCF_REQUIRE(!ema || !(overlaps(ema, params, n) || overlaps(ema, grads, n) || overlaps(ema, m, n) || overlaps(ema, v, n)),
+                "dcf_adamw_ema_step_groups: ema must not alias params, grads, m or v");
+    AdamGroupTable t;
+    t.frozen = 0xFFFFFFFFu;                               // an id past the table stores nothing
+    for (int k = 0; k < DCF_ADAM_MAX_GROUPS; ++k) t.mu[k] = 0.f, t.decay_mul[k] = 1.f;
+    for (int k = 0; k < ngroups; ++k) {
+        DCF_REQUIRE(isfinite(groups[k].mu) && groups[k].mu >= 0.f && isfinite(groups[k].decay_mul),
+                    "dcf_adamw_ema_step_groups: group %d: mu must be finite and not negative, decay_mul finite (got %g, %g)", k,
+                    (double)groups[k].mu, (double)groups[k].decay_mul);
+        t.mu[k] = groups[k].mu;
+        t.decay_mul[k] = groups[k].decay_mul;
+        if (!groups[k].frozen) t.frozen &= ~(1u << k);
+    }
+    if (n == 0) return DCF_OK;
+    AdamwScalars c;
+    c.b1 = beta1; c.b2 = beta2; c.eps = eps; c.decay_mul = 1.f; c.ema_omd = ema_omd;
+    c.lr_over_bc1 = c.inv_sqrt_bc2 = c.gscale = 0.f;
+    if (!state) {                                         // dcf_adam_step's host expressions
+        const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
+        c.lr_over_bc1 = (float)(lr / bc1);
+        c.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+        c.gscale = gscale;
+    }
+    static DcfOpt shape_o("ADAMW_SHAPE");
+    const char *shape = shape_o.str();
+    const bool stride = shape ? strcmp(shape, "stride") == 0 : false;
+    const int64_t ng4 = (n + 3) / 4;
+    const int blocks = stride ? (int)(cdiv(ng4, 2 * kThreads) < kMaxBlocks ? cdiv(ng4, 2 * kThreads) : kMaxBlocks) : cdiv(ng4, kThreads);
+    const double bytes = (double)n * (ema ? 36.0 : 28.0) + (double)n / 4.0 + (decay_bits ? (double)n / 32.0 : 0.0);
+    hipStream_t s = S(stream);
+#define DCF_ADAMW_G(GUARD_, EMA_)                                                                                                           \
+    do {                                                                                                                                     \
+        if (stride)                                                                                                                          \
+            DCF_LAUNCH_B("adamw_ema_groups", bytes, s, hipLaunchKernelGGL((k_adamw_groups_stride<GUARD_, EMA_>), dim3(blocks), dim3(kThreads), 0, \
+                                                                          s, params, grads, m, v, ema, decay_bits, group_ids, n, c, t, state)); \
+        else                                                                                                                                 \
+            DCF_LAUNCH_B("adamw_ema_groups", bytes, s, hipLaunchKernelGGL((k_adamw_groups_flat<GUARD_, EMA_>), dim3(blocks), dim3(kThreads), 0,  \
+                                                                          s, params, grads, m, v, ema, decay_bits, group_ids, n, c, t, state)); \
+    } while (0)
+    if (state && ema) DCF_ADAMW_G(true, true);
+    else if (state) DCF_ADAMW_G(true, false);
+    else if (ema) DCF_ADAMW_G(false, true);
+    else DCF_ADAMW_G(false, false);
+#undef DCF_ADAMW_G
+    return DCF_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
 // Gradient accumulation: dst = src (mode 0) or dst = dst + src (mode 1) over n floats, one fp32 add per
 // element, no atomics -- every element has one writer.  Called on the whole gradient arena and on sub-ranges of it (the gradient
 // buckets), so the pointers are only 4-byte aligned:

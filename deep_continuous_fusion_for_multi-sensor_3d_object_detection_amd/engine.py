@@ -400,6 +400,11 @@ class Plan(object):
         self.cf = cf
         self.table = ParamTable()
         self.layers = []
+        # fine-tuning (both off by default): image_norm = (mean, std) float32[3] of `fusion.image_norm` (the
+        # model sets it); img_frozen = length of the frozen prefix of the camera trunk (set_frozen_trunk: 0 none, 1 stem, 2 stem +
+        # layer1, ..., 5 the whole trunk), which leaves the backward plan
+        self.image_norm = None
+        self.img_frozen = 0
         lm = cfg["lidar_module"]
         self.widths = [lm["out_feature%d" % i] for i in range(1, 6)]
         self.nblocks = [lm["num_res_block%d" % i] for i in range(1, 6)]
@@ -644,15 +649,16 @@ class Plan(object):
     # ------------------------------------------------------------------ image stream
     def _image_forward(self, K, x_image, save):
         B, _, Hh, W = x_image.shape
-        img4 = K.image_to_nhwc4(x_image)
+        img4 = K.image_to_nhwc4(x_image) if self.image_norm is None else K.image_to_nhwc4_norm(x_image, self.image_norm[0], self.image_norm[1])
         c1 = K.stem_fwd(self.stem, img4, Hh, W)
-        if save:
+        nf = self.img_frozen                # frozen prefix: nothing is kept that only its (skipped) backward would read
+        if save and nf == 0:
             x, pool_idx = K.maxpool_fwd_idx(c1)
         else:
             x, pool_idx = K.maxpool_fwd(c1), None
         feats = []
-        for blocks in self.img_stages:
-            x = blocks_forward(K, blocks, x, save)
+        for li, blocks in enumerate(self.img_stages):
+            x = blocks_forward(K, blocks, x, save and li + 1 >= nf)
             feats.append(x)
         c2, c3, c4, c5 = feats
         # the four laterals only read the trunk's outputs: issued together, then the chain of resize-and-add passes
@@ -663,9 +669,28 @@ class Plan(object):
             if i == 0:
                 p2 = p
         fmap = K.conv_fwd(self.img_smooth, p2, None, False)
-        if save:
+        if save and nf:
+            self.ctx["img"] = dict(hw=(Hh, W), feats=feats, p2=p2)
+        elif save:
             self.ctx["img"] = dict(img4=img4, hw=(Hh, W), c1=c1, pool_idx=pool_idx, feats=feats, p2=p2)
         return fmap
+
+    def set_frozen_trunk(self, units):
+        """units: length of the frozen prefix of the camera trunk (optim.frozen_trunk_units).  Returns (lo, hi), the contiguous run
+        of layer-table rows the prefix holds -- the stem, then whole stages -- or None for an empty prefix."""
+        units = int(units)
+        if not 0 <= units <= 5 or (units and not self.with_image):
+            raise ValueError("frozen trunk prefix of %d units (0 .. 5, and only with the camera stream)" % units)
+        self.img_frozen = units
+        if units == 0:
+            return None
+        rows = [self.stem.idx]
+        for blocks in self.img_stages[:units - 1]:
+            for b in blocks:
+                rows += [L.idx for L in (b.conv1, b.conv2, getattr(b, "conv3", None), b.down) if L is not None]
+        lo, hi = min(rows), max(rows) + 1
+        assert sorted(rows) == list(range(lo, hi)), "the frozen prefix is not one run of layer rows"
+        return lo, hi
 
     def _image_backward(self, K, gF):
         im = self.ctx["img"]
@@ -679,6 +704,8 @@ class Plan(object):
             gps.append(K.resize_bwd(gps[i], (feats[i + 1].shape[1], feats[i + 1].shape[2]), False))
         for i in range(4):
             K.conv_wgrad(self.img_lat[i], feats[i], gps[i])
+        if self.img_frozen:
+            return self._image_backward_frozen(K, gps, feats)
         gfeat = conv_dgrad_group(K, [(self.img_lat[i], gps[i], tuple(feats[i].shape), None, None) for i in range(4)], 32)
         g = gfeat[3]
         masked = False
@@ -691,6 +718,24 @@ class Plan(object):
         gc1 = K.maxpool_bwd(im["c1"], g, None, im.get("pool_idx"))
         gc1 = K.bn_bwd(self.stem, K.relu_mask(gc1, im["c1"]))
         K.stem_wgrad(self.stem, im["img4"], gc1, im["hw"][0], im["hw"][1])
+
+    def _image_backward_frozen(self, K, gps, feats):
+        """The rest of _image_backward with a frozen trunk prefix (img_frozen >= 1: the stem and the first img_frozen - 1 stages):
+        the backward stops at the first live stage.  The laterals of frozen stages keep their weight gradient (queued by the caller:
+        they are image_fpn.*) and drop out of the grouped input-gradient launch; the first live stage's first block needs no input
+        gradient, has no `prev` and no joining gradient; no max-pool, stem ReLU / BN or stem weight gradient runs."""
+        fs = self.img_frozen - 1            # frozen stages
+        live = list(range(fs, 4))
+        gfeat = dict(zip(live, conv_dgrad_group(K, [(self.img_lat[i], gps[i], tuple(feats[i].shape), None, None) for i in live], 32)))
+        g, masked = gfeat.get(3), False
+        for li in range(3, fs - 1, -1):
+            first = li == fs
+            g, masked = blocks_backward(K, self.img_stages[li], g, masked, None if first else gfeat[li - 1],
+                                        None if first else self.img_stages[li - 1][-1], not first)
+            if li == 3:
+                K.bucket_ready(self.layers, "image_hi")
+        if fs == 4:
+            K.bucket_ready(self.layers, "image_hi")
 
     # ------------------------------------------------------------------ fusion
     def _fusion_forward(self, K, f, x, fmap, geom, site, save):

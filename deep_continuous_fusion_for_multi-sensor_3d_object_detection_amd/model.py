@@ -437,6 +437,15 @@ class ObjectDetection_DCF(_FlatParamModule):
         self._graphs = None
         self._plan = Plan(config, with_image=self.fusion_enabled, cf=self.cf, image_arch=str(fu.get("image_stream", "resnet18")))
         self._backend = None
+        # fine-tuning the camera stream (finetune.py).  fusion.image_norm: the input conversion becomes
+        # dcf_image_to_nhwc4_norm wherever the model runs (absent: today's entry and launch); fusion.image_input_order: the colour of
+        # the dataset's plane 0, used when fusion.image_pretrained is loaded (train.Train); bad values raise here
+        from . import finetune as FT
+        self._plan.image_norm = FT.parse_image_norm(fu.get("image_norm", None))
+        self.image_input_order = fu.get("image_input_order", "bgr")
+        if self.image_input_order not in FT.INPUT_ORDERS:
+            raise ValueError("fusion.image_input_order must be one of %s (got %r)" % (list(FT.INPUT_ORDERS), self.image_input_order))
+        self._frozen_rows = None
         if self.deterministic and self.fusion_enabled:
             bad = [f["cb"] for f in self._plan.fusion if f["cb"] not in DET_CHANNELS]
             if bad:
@@ -470,6 +479,31 @@ class ObjectDetection_DCF(_FlatParamModule):
         self._grid = grid
         self._graphs = None
 
+    def set_frozen_trunk(self, units):
+        """A frozen prefix of the camera trunk (optim.frozen_trunk_units: 0 none, 1 the stem, 2 stem + layer1, ..., 5 all of it)
+        leaves the backward plan: its layers run no backward, its layer-table rows are never finalised and its range of the
+        gradient arena stays exact zeros.  Only with bn_mode eval -- a frozen BatchNorm that follows batch statistics is not built.
+        Returns the arena range (a, b) of the prefix, or None."""
+        units = int(units)
+        if units and self.bn_mode != "eval":
+            raise ValueError("a frozen prefix of the camera trunk needs bn_mode: eval (got %r)" % (self.bn_mode,))
+        rows = self._plan.set_frozen_trunk(units)
+        self._frozen_rows = rows
+        if self._backend is not None:
+            self._backend.set_frozen_rows(rows)
+        self._graphs = None
+        if rows is None:
+            return None
+        layers = self._plan.layers
+        a, b = layers[rows[0]].w_off, layers[rows[1]].w_off
+        self._gradflat[a:b].zero_()
+        return a, b
+
+    def load_image_trunk(self, state_dict, input_order="rgb"):
+        """finetune.load_image_trunk on this model."""
+        from . import finetune as FT
+        return FT.load_image_trunk(self, state_dict, input_order)
+
     def load_state_dict(self, state_dict, strict=True):
         """Accepts the reference's checkpoints with or without DDP's 'module.' prefix (train.py:79)."""
         sd = {(k[7:] if k.startswith("module.") else k): v for k, v in state_dict.items()}
@@ -486,6 +520,7 @@ class ObjectDetection_DCF(_FlatParamModule):
                                        fp8_min_cin=int(self.config.get("fp8_min_cin", 128)) if self.fp8 else 0,
                                        fp8_min_blocks=int(self.config.get("fp8_min_blocks", 512)))
             self._backend.deterministic = self.deterministic
+            self._backend.set_frozen_rows(self._frozen_rows)
             if self.config.get("conv_chain") is not None:          # residual stages as chain launches (exclusive use of the GPU only)
                 self._backend.chain_enabled = bool(self.config["conv_chain"])
         return self._backend

@@ -49,6 +49,20 @@ def image_to_nhwc4(img_u8, dtype):
     return y
 
 
+def image_to_nhwc4_norm(img_u8, dtype, mean, std, out=None):
+    """dcf_image_to_nhwc4_norm: image_to_nhwc4 with ((x / 255) - mean[c]) / std[c] per plane c of the image's own order (three
+    rounded fp32 operations, finetune.normalize_image is the statement); mean, std: three host floats each."""
+    B, C, Hh, W = img_u8.shape
+    assert C == 3 and img_u8.dtype == torch.uint8
+    _chk(img_u8, "image")
+    mean, std = H.host_f32(mean).reshape(-1), H.host_f32(std).reshape(-1)
+    if mean.size != 3 or std.size != 3:
+        raise ValueError("image_to_nhwc4_norm: mean and std hold three values each (got %d, %d)" % (mean.size, std.size))
+    y = torch.empty((B, Hh + 6, W + 8, 4), dtype=H.torch_dtype(dtype), device=img_u8.device) if out is None else out
+    H.call("dcf_image_to_nhwc4_norm", dtype, img_u8, y, B, Hh, W, mean, std, H.stream_ptr())
+    return y
+
+
 # ------------------------------------------------------------------ convolution
 def conv2d_fwd(dtype, x, w, shift, res, kh, kw, stride, pad, relu, cout):
     B, Hh, W, Cin = x.shape
@@ -332,6 +346,43 @@ def adamw_ema_step(params, grads, m, v, lr, beta1, beta2, eps, step, gscale=1.0,
     (p' - ema) in the same pass.  state (AmpState): the guarded step -- lr, step and gscale then come from the device."""
     H.call("dcf_adamw_ema_step", params, grads, m, v, ema, decay_bits, params.numel(), lr, beta1, beta2, eps, step, gscale, decay_mul,
            ema_omd, None if state is None else state.raw, H.stream_ptr())
+
+
+class AdamGroups(object):
+    """The side table of dcf_adamw_ema_step_groups: `ids`, one uint8 per float4 group of the arena (optim.group_ids), checked on the
+    host HERE -- an id of `count` or more is refused -- and uploaded once; `count` groups."""
+
+    def __init__(self, ids, count, device):
+        ids = np.ascontiguousarray(np.asarray(ids))
+        if ids.dtype != np.uint8 or ids.ndim != 1:
+            raise ValueError("AdamGroups: ids must be a one-dimensional uint8 array (got %s, %d-d)" % (ids.dtype, ids.ndim))
+        count = int(count)
+        if not 1 <= count <= H.ADAM_MAX_GROUPS:
+            raise ValueError("AdamGroups: 1 to %d groups (got %d)" % (H.ADAM_MAX_GROUPS, count))
+        if ids.size and int(ids.max()) >= count:
+            raise ValueError("AdamGroups: group id %d with %d groups" % (int(ids.max()), count))
+        self.count = count
+        self.n_ids = int(ids.size)
+        self.ids = torch.from_numpy(ids.copy()).to(device) if ids.size else torch.zeros(1, dtype=torch.uint8, device=device)
+        self.table = (H.AdamGroup * count)()
+
+
+def adamw_ema_step_groups(params, grads, m, v, lr, beta1, beta2, eps, step, groups, table, gscale=1.0, decay_bits=None, ema=None,
+                          ema_omd=0.0, state=None):
+    """dcf_adamw_ema_step_groups (csrc/optim.hip): adamw_ema_step with parameter groups.  groups: AdamGroups (the per-float4 ids);
+    table: [(mu, decay_mul, frozen)] per group id, by value into the launch.  A frozen group's p, m, v, ema keep their bits and its
+    gradient is not read; the others run at lr * mu with their own decay_mul."""
+    n = params.numel()
+    if len(table) != groups.count:
+        raise ValueError("adamw_ema_step_groups: %d table rows for %d groups" % (len(table), groups.count))
+    if groups.n_ids != (n + 3) // 4:
+        raise ValueError("adamw_ema_step_groups: %d group ids for %d elements (one per float4 group)" % (groups.n_ids, n))
+    for k, (mu, dm, fz) in enumerate(table):
+        groups.table[k] = H.AdamGroup(float(mu), float(dm), 1 if fz else 0)
+    if n == 0:                                             # (an empty tensor has no address to pass)
+        return
+    H.call("dcf_adamw_ema_step_groups", params, grads, m, v, ema, decay_bits, groups.ids, groups.count, ctypes.addressof(groups.table), n,
+           lr, beta1, beta2, eps, step, gscale, ema_omd, None if state is None else state.raw, H.stream_ptr())
 
 
 def grad_accumulate(dst, src, mode):

@@ -156,3 +156,108 @@ def decay_bits(table_entries, n_params, exclude=()):
     padded[:groups] = bits
     by = np.packbits(padded.reshape(-1, 64), axis=1, bitorder="little")        # byte b of a word = its bits 8b .. 8b+7
     return np.ascontiguousarray(by).view("<u8").astype(np.uint64).reshape(-1)
+
+
+# ---------------------------------------------------------------------------------------------------------------- parameter groups
+# `param_groups`: a list of {match, lr_mult | frozen}; the first group whose `match` holds a substring of a
+# parameter's state-dict key wins, listed group i has id i + 1, and an unmatched parameter is group 0 (lr_mult 1, not frozen).
+GROUP_KEYS = ("match", "lr_mult", "frozen")
+MAX_GROUPS = 16                         # DCF_ADAM_MAX_GROUPS: group 0 + at most 15 listed groups
+TRUNK = "image_backbone."
+
+
+def parse_param_groups(blk, keys=None):
+    """The `param_groups` list, validated: None (absent or empty) or [{"match": tuple of substrings, "lr_mult": float >= 0,
+    "frozen": bool}].  keys (the model's parameter keys): a group that wins no parameter raises too."""
+    if blk is None:
+        return None
+    if not isinstance(blk, (list, tuple)):
+        raise ValueError("param_groups must be a list of groups (got %r)" % (blk,))
+    if len(blk) == 0:
+        return None
+    if len(blk) > MAX_GROUPS - 1:
+        raise ValueError("param_groups: at most %d groups (got %d)" % (MAX_GROUPS - 1, len(blk)))
+    out = []
+    for i, g in enumerate(blk):
+        name = "param_groups[%d]" % i
+        if not isinstance(g, dict):
+            raise ValueError("%s must be a mapping (got %r)" % (name, g))
+        unknown = sorted(set(g) - set(GROUP_KEYS))
+        if unknown:
+            raise ValueError("%s: unknown keys %s (known: %s)" % (name, unknown, list(GROUP_KEYS)))
+        match = g.get("match", None)
+        if not isinstance(match, (list, tuple)) or len(match) == 0 or any(not isinstance(s, str) or not s for s in match):
+            raise ValueError("%s.match must be a non-empty list of non-empty strings (got %r)" % (name, match))
+        frozen = _flag(name + ".frozen", g.get("frozen", False))
+        if frozen and "lr_mult" in g:
+            raise ValueError("%s: frozen and lr_mult exclude each other" % name)
+        mult = _number(name + ".lr_mult", g.get("lr_mult", 1.0))
+        out.append({"match": tuple(match), "lr_mult": mult, "frozen": frozen})
+    if keys is not None:
+        won = set(group_of(k, out) for k in keys)
+        idle = [i for i in range(len(out)) if i + 1 not in won]
+        if idle:
+            raise ValueError("param_groups: groups %s match no parameter (first match wins)" % ([out[i]["match"] for i in idle],))
+    return out
+
+
+def group_of(key, groups):
+    """Id of the parameter group of state-dict key `key`: 1 + the index of the first listed group with a matching substring, else 0."""
+    for i, g in enumerate(groups or ()):
+        if any(s in key for s in g["match"]):
+            return i + 1
+    return 0
+
+
+def group_ids(table_entries, n_params, groups):
+    """The id array of dcf_adamw_ema_step_groups from engine.ParamTable.entries: uint8[ceil(n / 4)], one id per float4 group of the
+    arena.  Built as decay_bits is: a tensor names its whole PHYSICAL extent (layout padding and the up to three padding elements
+    behind it included), and ParamTable's 16-byte alignment -- no float4 group holds elements of two tensors -- is asserted.
+    Groups no tensor covers keep id 0."""
+    ids = np.zeros((int(n_params) + 3) // 4, dtype=np.uint8)
+    for key, shape, off, n, layout in table_entries:
+        if off % 4:
+            raise ValueError("parameter %s starts at element %d: not 16-byte aligned" % (key, off))
+        if off + n > n_params:
+            raise ValueError("parameter %s ends behind the arena (%d + %d > %d)" % (key, off, n, n_params))
+        ids[off // 4:(off + n + 3) // 4] = group_of(key, groups)
+    return ids
+
+
+def group_table(groups, lr, weight_decay=0.0):
+    """[(mu, decay_mul, frozen)] per group id 0 .. len(groups) for an optimiser call at rate lr (float64): decay_mul_g =
+    fl32(1 - lr * mu_g * weight_decay), formed in float64 and rounded once, as the single decay_mul of dcf_adamw_ema_step is."""
+    rows = [(1.0, False)] + [(0.0 if g["frozen"] else g["lr_mult"], g["frozen"]) for g in (groups or ())]
+    return [(float(mu), float(np.float32(1.0 - float(lr) * float(mu) * float(weight_decay))), bool(fz)) for mu, fz in rows]
+
+
+def group_rates(groups, lr):
+    """Rates of the next call per group id (host floats): lr * mu_g, 0.0 for a frozen group."""
+    return [float(lr) * mu for mu, _, _ in group_table(groups, lr)]
+
+
+def frozen_trunk_units(keys, groups):
+    """Length of the frozen PREFIX of the camera trunk: 0 = none, 1 = the stem (image_backbone.conv1 + .bn1), 2 = stem + layer1, ...,
+    5 = stem + all four stages.  A unit counts when it has parameters and every one of them lies in a frozen group; the prefix ends
+    at the first unit that does not (a frozen layer1 behind a live stem gives 0: its input gradient is still needed)."""
+    if not groups:
+        return 0
+    units = [[] for _ in range(5)]
+    for k in keys:
+        if not k.startswith(TRUNK):
+            continue
+        rest = k[len(TRUNK):]
+        if rest.startswith("conv1.") or rest.startswith("bn1."):
+            units[0].append(k)
+        else:
+            for li in range(1, 5):
+                if rest.startswith("layer%d." % li):
+                    units[li].append(k)
+    n = 0
+    for li, ks in enumerate(units):
+        gid = [group_of(k, groups) for k in ks]
+        stem_whole = li != 0 or (any(TRUNK + "conv1." in k for k in ks) and any(TRUNK + "bn1." in k for k in ks))
+        if not ks or not stem_whole or any(g == 0 or not groups[g - 1]["frozen"] for g in gid):
+            break
+        n = li + 1
+    return n

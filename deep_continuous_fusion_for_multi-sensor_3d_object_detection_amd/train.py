@@ -296,9 +296,12 @@ class FlatAdam(object):
     k), k = opt_calls, the host's count of step() calls (a step the guard skips on the device still counts; the bias correction
     keeps the applied count).  With weight_decay > 0 or ema_decay set the step is dcf_adamw_ema_step (csrc/optim.hip) instead of
     dcf_adam_step / dcf_adam_step_guarded: decoupled decay on the tensors of optim.decay_bits, and `ema`, a second arena that
-    follows the parameters, both in the Adam pass.  None: the launches, arguments and allocations of the plain optimiser."""
+    follows the parameters, both in the Adam pass.  None: the launches, arguments and allocations of the plain optimiser.
+    groups (optim.parse_param_groups): the step is ALWAYS dcf_adamw_ema_step_groups, whether or not decay or
+    the average are configured -- group g runs at lr * lr_mult_g with decay_mul_g = 1 - lr * lr_mult_g * weight_decay, a frozen group
+    keeps p, m, v and the average bit for bit and its gradient is not read.  None: exactly the calls above."""
 
-    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, guard=None, recipe=None):
+    def __init__(self, model, lr, betas=(0.9, 0.999), eps=1e-8, guard=None, recipe=None, groups=None):
         self.model, self.lr, self.betas, self.eps = model, lr, betas, eps
         self._step_count = 0
         self.m = torch.zeros_like(model.flat_params)
@@ -317,6 +320,10 @@ class FlatAdam(object):
             self.ema = model.flat_params.detach().clone()
             self._ema_fresh = True
         self.fused = self.decay_bits is not None or self.ema is not None
+        self.groups, self.group_ids = groups, None
+        if groups is not None:
+            n = model.flat_params.numel()
+            self.group_ids = ops.AdamGroups(OPT.group_ids(model._table.entries, n, groups), len(groups) + 1, model.flat_params.device)
 
     def seed_ema(self):
         """Before the first optimiser call (or a checkpoint) the average follows the parameters; no-op afterwards."""
@@ -325,6 +332,10 @@ class FlatAdam(object):
 
     def lr_at(self, k):
         return OPT.lr_at(self.recipe["schedule"], self.lr, k) if self.recipe is not None else self.lr
+
+    def group_rates(self, k):
+        """Rates of optimiser call k per parameter-group id (host floats; [the one rate] without param_groups)."""
+        return OPT.group_rates(self.groups, self.lr_at(k))
 
     @property
     def step_count(self):
@@ -353,6 +364,8 @@ class FlatAdam(object):
                 self.seed_ema()
                 self._ema_fresh = False
                 omd = 1.0 - OPT.ema_decay_at(self.recipe, k)
+        if self.groups is not None:
+            return self._step_groups(lr, gscale, omd)
         if self.amp is not None:
             g = self.guard
             ops.grad_stats(self.model.flat_grads, self.amp)
@@ -372,6 +385,23 @@ class FlatAdam(object):
         else:
             ops.adam_step(self.model.flat_params, self.model.flat_grads, self.m, self.v, lr, self.betas[0], self.betas[1],
                           self.eps, self._step_count, gscale)
+
+    def _step_groups(self, lr, gscale, omd):
+        """step() with param_groups: the guard's scan and norm run over the WHOLE arena (a frozen tensor whose gradient the backward
+        still computes counts; the frozen trunk prefix contributes exact zeros), then the one grouped pass."""
+        wd = self.recipe["weight_decay"] if self.recipe is not None else 0.0
+        table = OPT.group_table(self.groups, lr, wd)
+        if self.amp is not None:
+            g = self.guard
+            ops.grad_stats(self.model.flat_grads, self.amp)
+            ops.amp_update(self.amp, gscale, g["mode"] == "dynamic", g["growth_factor"], g["backoff_factor"], g["growth_interval"],
+                           g["max_norm"], lr, self.betas[0], self.betas[1])
+            step = 0
+        else:
+            self._step_count += 1
+            step = self._step_count
+        ops.adamw_ema_step_groups(self.model.flat_params, self.model.flat_grads, self.m, self.v, lr, self.betas[0], self.betas[1], self.eps,
+                                  step, self.group_ids, table, gscale, self.decay_bits, self.ema, omd, self.amp)
 
     def state_dict(self):
         sd = {"step": self.step_count, "m": self.m, "v": self.v, "opt_calls": self.opt_calls}
@@ -444,7 +474,20 @@ class Train(nn.Module):
         self.guard = parse_guard_config(config)
         # training recipe (lr_schedule / weight_decay / ema_decay; None = the constant-rate Adam step, the default)
         self.recipe = OPT.parse_optim_config(config)
-        self.optimizer = FlatAdam(self.model, config["learning_rate"], (config["beta1"], 0.999), guard=self.guard, recipe=self.recipe)
+        # fine-tuning the camera stream (finetune.py; all off by default).  fusion.image_pretrained: a
+        # torchvision-layout trunk, loaded on every rank before sync_replicas().  param_groups: per-group rate multipliers and frozen
+        # groups in the optimiser pass; the longest frozen PREFIX of the camera trunk (stem, then whole stages) also leaves the
+        # backward plan -- frozen_range = its arena range (exact zeros in the gradient arena), None when there is none
+        pre = (config.get("fusion") or {}).get("image_pretrained", None)
+        if pre is not None:
+            from . import finetune as FT
+            FT.load_image_trunk_file(self.model, pre, self.model.image_input_order)
+        keys = [e[0] for e in self.model._table.entries]
+        self.param_groups = OPT.parse_param_groups(config.get("param_groups", None), keys)
+        units = OPT.frozen_trunk_units(keys, self.param_groups)
+        self.frozen_range = self.model.set_frozen_trunk(units) if units else None
+        self.optimizer = FlatAdam(self.model, config["learning_rate"], (config["beta1"], 0.999), guard=self.guard, recipe=self.recipe,
+                                  groups=self.param_groups)
         self._ema_swapped = False
         self.sync_replicas()
         self._side = None
@@ -969,6 +1012,11 @@ class Train(nn.Module):
         """The rate the NEXT optimiser call runs at (host float: the schedule is a function of the host's call count)."""
         return float(self.optimizer.lr_at(self.optimizer.opt_calls))
 
+    def learning_rates(self):
+        """The rates the NEXT optimiser call runs at, per parameter-group id (host floats, no device read): entry 0 is the base
+        group's, entry i the i-th listed group's (0.0 when frozen); one entry without param_groups."""
+        return self.optimizer.group_rates(self.optimizer.opt_calls)
+
     def ema_params(self):
         """The averaged weights: a device arena laid out like model.flat_params (the tensor itself); None without ema_decay."""
         if self.optimizer.ema is None:
@@ -1210,7 +1258,10 @@ def main():
             torch.save(training.model.state_dict(), "./saved_model/" + config["saved_model_name"])
             if training.ema_params() is not None:                          # the averaged weights beside the model, same key names
                 torch.save(training.ema_state_dict(), "./saved_model/" + config["saved_model_name"] + "_ema")
-            print("epoch %d: learning rate %.6g" % (epoch, training.learning_rate()))
+            if training.param_groups is None:
+                print("epoch %d: learning rate %.6g" % (epoch, training.learning_rate()))
+            else:
+                print("epoch %d: learning rate %.6g, per parameter group %s" % (epoch, training.learning_rate(), " ".join("%.6g" % r for r in training.learning_rates())))
         terms_sum, terms_n = None, 0                                       # focal: the epoch's mean terms, added up on the device
         pasted, pasted_frames = 0, 0                                       # augment_paste: accepted objects / frames of the epoch
         occluders, covering = 0, 0                                         # camera_mask.paste_occlusion: occluding patches / dropped objects

@@ -210,6 +210,12 @@ int dcf_nchw_to_nhwc(int dtype, const float *x, void *y, int B, int C, int H, in
 int dcf_nhwc_to_nchw(int dtype, const void *x, float *y, int B, int C, int H, int W, dcf_stream_t stream);
 /* uint8 NCHW image -> x/255 as NHWC with C padded to 4 and a zero halo of 3 pixels (stem input). */
 int dcf_image_to_nhwc4(int dtype, const uint8_t *img, void *y, int B, int H, int W, dcf_stream_t stream);
+/* (version 202 still: an addition) The same with the input normalisation of `fusion.image_norm`: per plane c
+ * of the input's own order and byte s,  v = fl(fl(fl((float)s / 255) - mean[c]) / std[c])  -- three correctly rounded fp32
+ * operations, nothing contracted, no reciprocal.  Halo pixels and channel 3 are +0.  mean, std: HOST float[3], copied into the kernel
+ * argument; mean finite, std finite and > 0.  With mean = 0 and std = 1 every stored bit is dcf_image_to_nhwc4's. */
+int dcf_image_to_nhwc4_norm(int dtype, const uint8_t *img, void *y, int B, int H, int W, const float *mean, const float *std,
+                            dcf_stream_t stream);
 
 /* -------------------------------------------------------------- convolution
  * Replaces nn.Conv2d (+ folded eval BatchNorm + residual + ReLU) of model.py:15-41,147-157.
@@ -554,6 +560,26 @@ int dcf_adam_step_guarded(float *params, const float *grads, float *m, float *v,
 int dcf_adamw_ema_step(float *params, const float *grads, float *m, float *v, float *ema, const uint64_t *decay_bits, int64_t n,
                        float lr, float beta1, float beta2, float eps, int step, float gscale, float decay_mul, float ema_omd,
                        const dcf_amp_state *state, dcf_stream_t stream);
+
+/* (version 202 still: the entry adds to the ABI without changing any of it; probe for the symbol) Parameter groups in the optimiser
+ * pass (`param_groups`; csrc/optim.hip): dcf_adamw_ema_step with a second side table.  group_ids (device) holds
+ * one byte per float4 group of the arena (ceil(n/4) bytes; group j = elements 4j .. 4j+3), the id g of the group's parameter group,
+ * 0 .. ngroups-1; groups (HOST, ngroups <= DCF_ADAM_MAX_GROUPS entries, copied into the kernel argument) holds per id
+ * {mu, decay_mul, frozen}.  Per element of a float4 group with id g, fp32, nothing contracted:
+ *     frozen_g :  skipped -- g is not read and p, m, v, e are not stored: they keep their bits whatever g holds (NaN included)
+ *     else     :  gk, m', v' as dcf_adamw_ema_step ;  q = decays(i) ? p * decay_mul_g : p
+ *                 lr_g = lr_over_bc1 * mu_g                                  (one fp32 product; lr_over_bc1 as in dcf_adamw_ema_step)
+ *                 p' = q - lr_g * m' / (sqrtf(v') * inv_sqrt_bc2 + eps) ;  e' = e + ema_omd * (p' - e)       (ema != NULL only)
+ * decay_mul_g = (float)(1 - lr * mu_g * weight_decay) comes from the host.  With mu == 1, decay_mul_g == decay_mul and nothing frozen
+ * the stores are dcf_adamw_ema_step's bits.  state != NULL: the guarded form, found_inf set stores nothing.  Alignment and aliasing
+ * rules are dcf_adamw_ema_step's; mu must be finite and >= 0, decay_mul finite.  An id of ngroups or more (the ids live on the device:
+ * the caller checks them where it builds them) makes its float4 group behave as frozen. */
+#define DCF_ADAM_MAX_GROUPS 16
+typedef struct { float mu, decay_mul; int32_t frozen; } dcf_adam_group;
+int dcf_adamw_ema_step_groups(float *params, const float *grads, float *m, float *v, float *ema, const uint64_t *decay_bits,
+                              const uint8_t *group_ids, int ngroups, const dcf_adam_group *groups, int64_t n, float lr, float beta1,
+                              float beta2, float eps, int step, float gscale, float ema_omd, const dcf_amp_state *state,
+                              dcf_stream_t stream);
 
 /* (version 202 still: tests/test_amp_host.py pins the number, and the entry adds to the ABI without changing any of it; probe for the
  * symbol) Gradient accumulation (`grad_accum_steps`; csrc/optim.hip): one streaming pass over n floats,
