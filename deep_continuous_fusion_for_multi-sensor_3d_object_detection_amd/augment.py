@@ -20,7 +20,33 @@ import math
 
 import numpy as np
 
+from . import cfgcheck as C
+
 M64 = (1 << 64) - 1
+KEYS = ("enabled", "seed", "rotation_deg", "scale", "flip_prob", "point_drop")
+
+
+def parse_config(config):
+    """The `augment` block (config_carla.yaml), validated: None = off (no block, or enabled: false), else {"seed", "rotation_deg",
+    "scale": (lo, hi), "flip_prob", "point_drop": (lo, hi)}.  Bad values raise ValueError whether the block is enabled or not --
+    augmentation is never switched off quietly."""
+    got = C.seeded_block(config, "augment", KEYS)
+    if got is None:
+        return None
+    blk, enabled, seed = got
+    rot = C.number("augment.rotation_deg", blk.get("rotation_deg", 0.0))
+    if rot < 0.0:
+        raise ValueError("augment.rotation_deg: theta ~ U(-r, +r) needs r >= 0 (got %r)" % (rot,))
+    scale = C.interval("augment.scale", blk.get("scale", (1.0, 1.0)))
+    if scale[0] <= 0.0:
+        raise ValueError("augment.scale must be positive (got %r)" % (blk.get("scale"),))
+    flip = C.probability("augment.flip_prob", blk.get("flip_prob", 0.0))
+    drop = C.interval("augment.point_drop", blk.get("point_drop", (0.0, 0.0)))
+    for p in drop:
+        C.probability("augment.point_drop", p)
+    if not enabled:
+        return None
+    return {"seed": seed, "rotation_deg": rot, "scale": scale, "flip_prob": flip, "point_drop": drop}
 
 
 def mix64(z):
@@ -52,7 +78,7 @@ _THETA, _SCALE, _FLIP, _DROP_P, _DROP_KEY = range(5)
 def draw(cfg, seed, rank, call, b):
     """Parameters of frame b of the call-th augmented step on `rank`: theta ~ U(-rotation_deg, +rotation_deg), s ~ U(scale),
     flip with probability flip_prob, p ~ U(point_drop), and the 64-bit key of the point-drop hash.  cfg: the dict of
-    train.parse_augment_config (or any dict with those keys)."""
+    parse_config (or any dict with those keys)."""
     base = (int(seed) * 0x9E3779B1 + int(call) + int(rank) * 0x85EBCA77C2B2AE63) & M64      # LossTotal._step_seed's formula
 
     def h(stream):

@@ -24,12 +24,41 @@ mix64 construction) on hash streams 16..25 -- the BEV block owns 0..4 -- so both
 """
 import numpy as np
 
+from . import cfgcheck as C
 from .augment import M64, mix64
 
 NQ = 8                     # ku cu kv cv g0 g1 g2 bias
 # one hash stream per drawn value (augment.py holds 0..4)
 _ZOOM, _DX, _DY, _FLIP, _BRIGHT, _CONTRAST, _GAIN0, _GAIN1, _GAIN2, _DROP = range(16, 26)
 _STREAMS = np.arange(16, 26, dtype=np.uint64)
+KEYS = ("enabled", "seed", "zoom", "shift", "flip_prob", "brightness", "contrast", "channel_gain", "drop_prob")
+
+
+def _factor_interval(blk, key, least=None):
+    """blk[key] (default [1, 1]) as an interval of positive factors, lo >= least where given."""
+    lo, hi = C.interval("augment_image." + key, blk.get(key, (1.0, 1.0)))
+    if lo <= 0.0 or (least is not None and lo < least):
+        raise ValueError("augment_image.%s must be %s (got %r)" % (key, "positive" if least is None else ">= %g" % least, blk.get(key)))
+    return lo, hi
+
+
+def parse_config(config):
+    """The `augment_image` block, validated like `augment`: None = off (no block, or enabled: false), else {"seed", "zoom": (lo, hi),
+    "shift": (fx, fy), "flip_prob", "brightness": (lo, hi), "contrast": (lo, hi), "channel_gain": (lo, hi), "drop_prob"}.  Bad values
+    raise ValueError whether the block is enabled or not.  zoom needs lo >= 0.5: the two-tap bilinear of the kernel covers every
+    source pixel only up to a 2x minification (a bound derived from the filter's footprint, not a measured one)."""
+    got = C.seeded_block(config, "augment_image", KEYS)
+    if got is None:
+        return None
+    blk, enabled, seed = got
+    zoom = _factor_interval(blk, "zoom", least=0.5)
+    shift = C.pair("augment_image.shift", blk.get("shift", (0.0, 0.0)))
+    if not (0.0 <= shift[0] <= 0.5 and 0.0 <= shift[1] <= 0.5):
+        raise ValueError("augment_image.shift: fractions of the width and height in [0, 0.5] (got %r)" % (blk.get("shift"),))
+    out = {"seed": seed, "zoom": zoom, "shift": shift, "flip_prob": C.probability("augment_image.flip_prob", blk.get("flip_prob", 0.0)),
+           "brightness": _factor_interval(blk, "brightness"), "contrast": _factor_interval(blk, "contrast"),
+           "channel_gain": _factor_interval(blk, "channel_gain"), "drop_prob": C.probability("augment_image.drop_prob", blk.get("drop_prob", 0.0))}
+    return out if enabled else None
 
 
 def params_from(width, height, zoom=1.0, flip=False, dx=0.0, dy=0.0, brightness=1.0, contrast=1.0, gain=(1.0, 1.0, 1.0), drop=False):
@@ -55,7 +84,7 @@ def draw(cfg, seed, rank, call, b, width, height):
     """Parameters of frame b of the call-th augmented step on `rank` for a [3, height, width] image: s ~ U(zoom),
     dx ~ U(-fx W, fx W), dy ~ U(-fy H, fy H) with (fx, fy) = shift, a flip with probability flip_prob, beta ~ U(brightness),
     kappa ~ U(contrast), gamma_c ~ U(channel_gain) per channel, the frame blacked out with probability drop_prob.  cfg: the dict
-    of train.parse_image_augment_config (or any dict with those keys)."""
+    of parse_config (or any dict with those keys)."""
     base = (int(seed) * 0x9E3779B1 + int(call) + int(rank) * 0x85EBCA77C2B2AE63) & M64      # augment.draw's formula
 
     # the ten streams in one vectorised hash (the values of augment.draw's h(stream), two numpy calls instead of twenty)

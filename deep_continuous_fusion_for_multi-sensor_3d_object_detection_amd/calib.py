@@ -24,6 +24,12 @@ def crt_from(K, R):
     return np.ascontiguousarray(np.matmul(np.asarray(K, dtype=np.float64), RT).T.astype(np.float32))
 
 
+def own_crts(default, crts, n):
+    """The n frames' own [4,3] matrices: crts[b] where the batch carries one (KITTI calibrates every frame), else `default`, the
+    geometry's."""
+    return [default if (crts is None or crts[b] is None) else crts[b] for b in range(n)]
+
+
 def carla_crt():
     """data_import_carla.py:180-194: CARLA intrinsics and the euler-difference extrinsic."""
     v_lidar = np.array([-1.57079633, 3.12042851, -1.57079633])

@@ -111,8 +111,7 @@ class FrameGeometry(object):
         if not (1 <= len(pts) <= 8) or any(p.shape[0] > mp_ for p in pts):
             return False
         ulim, vlim = self.limits()
-        mats = np.stack([np.ascontiguousarray(self.crt if (crts is None or crts[b] is None) else crts[b], dtype=np.float32).reshape(12)
-                         for b in range(len(pts))], 0)
+        mats = np.stack([np.ascontiguousarray(m, dtype=np.float32).reshape(12) for m in calib.own_crts(self.crt, crts, len(pts))], 0)
         self._proj_ws = ops.project_filter_batch(pts, self.grid.lim, mats, ulim, vlim, self.proj_mode, uv_all, xyz_all, cnt_all,
                                                  getattr(self, "_proj_ws", None))
         return True
@@ -127,8 +126,7 @@ class FrameGeometry(object):
         if out is None:
             out = [torch.empty_like(p) for p in pts]
         ulim, vlim = self.limits()
-        mats = np.stack([np.ascontiguousarray(self.crt if (crts is None or crts[b] is None) else crts[b], dtype=np.float32).reshape(12)
-                         for b in range(len(pts))], 0)
+        mats = np.stack([np.ascontiguousarray(m, dtype=np.float32).reshape(12) for m in calib.own_crts(self.crt, crts, len(pts))], 0)
         ops.camera_mask_points_batch(pts, mats, self.grid.lim, ulim, vlim, self.proj_mode, fov, occluders, list(out))
         return [o[:p.shape[0]] for o, p in zip(out, pts)]
 

@@ -5,10 +5,10 @@ Plain numpy / torch host code; nothing here imports torchvision or reads the dev
 (csrc/elementwise.hip, dcf_image_to_nhwc4_norm) is pinned to normalize_image bit for bit; the parameter groups that go with a loaded
 trunk are optim.parse_param_groups / optim.group_ids.
 """
-import math
-
 import numpy as np
 import torch
+
+from . import cfgcheck as C
 
 NORM_KEYS = ("mean", "std")
 INPUT_ORDERS = ("rgb", "bgr")
@@ -20,20 +20,13 @@ def parse_image_norm(blk):
     the dataset delivers.  Unknown keys, wrong lengths, a non-finite mean and a std that is not finite and > 0 raise ValueError."""
     if blk is None:
         return None
-    if not isinstance(blk, dict):
-        raise ValueError("fusion.image_norm must be a mapping with mean and std (got %r)" % (blk,))
-    unknown = sorted(set(blk) - set(NORM_KEYS))
-    if unknown:
-        raise ValueError("fusion.image_norm: unknown keys %s (known: %s)" % (unknown, list(NORM_KEYS)))
+    C.block("fusion.image_norm", blk, NORM_KEYS)
     out = []
     for key in NORM_KEYS:
         v = blk.get(key, None)
         if not isinstance(v, (list, tuple)) or len(v) != 3:
             raise ValueError("fusion.image_norm.%s must be a list of three numbers (got %r)" % (key, v))
-        for x in v:
-            if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(float(x)):
-                raise ValueError("fusion.image_norm.%s must hold finite numbers (got %r)" % (key, v))
-        a = np.asarray(v, dtype=np.float32)
+        a = np.asarray([C.number("fusion.image_norm." + key, x) for x in v], dtype=np.float32)
         if not np.isfinite(a).all() or (key == "std" and not (a > 0).all()):
             raise ValueError("fusion.image_norm.%s: %s (got %r)" % (key, "must be greater than 0 in fp32" if key == "std" else "overflows fp32", v))
         out.append(a)

@@ -509,6 +509,53 @@ def project_filter_batch(pts_list, lim, crts, ulim, vlim, mode, uv_all, xyz_all,
     return ws
 
 
+def _check_point_frames(op, pts_list, out_list, bank=None):
+    """The frame checks of the point wrappers (augment, camera mask, paste): contiguous fp32 CUDA tensors, and an output holds at
+    least its frame.  bank (paste): frames, outputs and the bank are [n,3]; the capacity of an output is the kernel's to check."""
+    n3 = bank is not None
+    for t in list(pts_list) + list(out_list) + ([bank] if n3 else []):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and (not n3 or (t.dim() == 2 and t.shape[1] == 3))):
+            raise H.DcfError("%s: %s must be contiguous fp32 CUDA tensors%s" % (op, "frames, outputs and the bank" if n3 else "frames", " [n,3]" if n3 else ""))
+    if not n3 and any(o.numel() < p.numel() for p, o in zip(pts_list, out_list)):
+        raise H.DcfError("%s: output smaller than its frame" % op)
+
+
+def _chunk_tables(pts, outs, null_by_output=False):
+    """(k, ptrs, outs, ns): the pointer and row-count tables of one chunk of k <= 8 frames.  A frame without rows travels as a null
+    pointer, and so does its output -- null_by_output (paste, whose outputs hold more rows than their frames): an output is null
+    when it has no rows itself."""
+    k = len(pts)
+    ptrs = (ctypes.c_void_p * k)(*[p.data_ptr() if p.shape[0] else None for p in pts])
+    optrs = (ctypes.c_void_p * k)(*[o.data_ptr() if (o if null_by_output else p).shape[0] else None for p, o in zip(pts, outs)])
+    ns = (ctypes.c_int * k)(*[int(p.shape[0]) for p in pts])
+    return k, ptrs, optrs, ns
+
+
+def _check_image_pair(op, img_u8, out, count, what, also=(), out_optional=False):
+    """The checks of a uint8 [B,3,H,W] image and the output beside it (DcfError), with the overlap test (ValueError: neither kernel works in
+    place -- the augmentation gathers neighbouring pixels, the batch's image is a view of the loader's staging set).  count: how many
+    per-frame `what` came with the image; also: further (name, tensor) byte buffers; out None where out_optional: a new tensor.
+    Returns (out, B, H, W)."""
+    for name, t in (("img_u8", img_u8), ("out", out)) + tuple(also):
+        if t is None and name == "out" and out_optional:
+            continue
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+            raise H.DcfError("%s: %s must be a contiguous uint8 CUDA tensor" % (op, name))
+    if img_u8.dim() != 4 or img_u8.shape[1] != 3 or img_u8.numel() == 0:
+        raise H.DcfError("%s: image must be [B,3,H,W] (got %s)" % (op, tuple(img_u8.shape)))
+    B, _, Hh, Ww = (int(v) for v in img_u8.shape)
+    if count != B:
+        raise H.DcfError("%s: %d frames, %d %s" % (op, B, count, what))
+    if out is None:
+        out = torch.empty_like(img_u8)
+    if tuple(out.shape) != tuple(img_u8.shape) or out.device != img_u8.device:
+        raise H.DcfError("%s: out must be %s on the image's device" % (op, tuple(img_u8.shape)))
+    nbytes = img_u8.numel()
+    if img_u8.data_ptr() < out.data_ptr() + nbytes and out.data_ptr() < img_u8.data_ptr() + nbytes:
+        raise ValueError("%s: out overlaps the input" % op)
+    return out, B, Hh, Ww
+
+
 def augment_points_batch(pts_list, params, out_list=None):
     """Train-time BEV augmentation (augment.py) of the frames of a batch: pts_list = B device tensors [n_b,3]
     fp32 (views at any point offset of a larger buffer included), params = B augment.draw results; out_list: B tensors to write
@@ -519,18 +566,10 @@ def augment_points_batch(pts_list, params, out_list=None):
     if len(params) != B or (out_list is not None and len(out_list) != B):
         raise H.DcfError("augment_points_batch: %d frames, %d parameter sets" % (B, len(params)))
     out_list = pts_list if out_list is None else out_list
-    for p, o in zip(pts_list, out_list):
-        for t in (p, o):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
-                raise H.DcfError("augment_points_batch: frames must be contiguous fp32 CUDA tensors")
-        if o.numel() < p.numel():
-            raise H.DcfError("augment_points_batch: output smaller than its frame")
+    _check_point_frames("augment_points_batch", pts_list, out_list)
     for b0 in range(0, B, 8):
         sl = slice(b0, min(b0 + 8, B))
-        k = sl.stop - sl.start
-        ptrs = (ctypes.c_void_p * k)(*[p.data_ptr() if p.shape[0] else None for p in pts_list[sl]])
-        outs = (ctypes.c_void_p * k)(*[o.data_ptr() if p.shape[0] else None for p, o in zip(pts_list[sl], out_list[sl])])
-        ns = (ctypes.c_int * k)(*[int(p.shape[0]) for p in pts_list[sl]])
+        k, ptrs, outs, ns = _chunk_tables(pts_list[sl], out_list[sl])
         mat = np.ascontiguousarray(np.stack([augment.matrix5(q) for q in params[sl]], 0), dtype=np.float32)
         keys = (ctypes.c_uint64 * k)(*[int(q["drop_key"]) for q in params[sl]])
         thr = (ctypes.c_uint32 * k)(*[augment.drop_threshold(q) for q in params[sl]])
@@ -550,16 +589,11 @@ def camera_mask_points_batch(pts_list, crts, lim, ulim, vlim, mode, fov, occ_lis
         raise H.DcfError("camera_mask_points_batch: %d frames, %s outputs, %s occluder sets"
                          % (B, "no" if out_list is None else len(out_list), "no" if occ_list is None else len(occ_list)))
     out_list = pts_list if out_list is None else out_list
-    for p, o in zip(pts_list, out_list):
-        for t in (p, o):
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
-                raise H.DcfError("camera_mask_points_batch: frames must be contiguous fp32 CUDA tensors")
-        if o.numel() < p.numel():
-            raise H.DcfError("camera_mask_points_batch: output smaller than its frame")
+    _check_point_frames("camera_mask_points_batch", pts_list, out_list)
     crt = np.ascontiguousarray(np.asarray(crts, dtype=np.float32).reshape(B, 12))
     for b0 in range(0, B, 8):
         sl = slice(b0, min(b0 + 8, B))
-        k = sl.stop - sl.start
+        k, ptrs, outs, ns = _chunk_tables(pts_list[sl], out_list[sl])
         occ = np.zeros((k, 16, 5), dtype=np.float32)
         ms = (ctypes.c_int * k)()
         for i in range(k):
@@ -571,9 +605,6 @@ def camera_mask_points_batch(pts_list, crts, lim, ulim, vlim, mode, fov, occ_lis
                 raise H.DcfError("camera_mask_points_batch: a frame holds at most 16 occluders (got %d)" % len(q))
             ms[i] = len(q)
             occ[i, :len(q)] = q
-        ptrs = (ctypes.c_void_p * k)(*[p.data_ptr() if p.shape[0] else None for p in pts_list[sl]])
-        outs = (ctypes.c_void_p * k)(*[o.data_ptr() if p.shape[0] else None for p, o in zip(pts_list[sl], out_list[sl])])
-        ns = (ctypes.c_int * k)(*[int(p.shape[0]) for p in pts_list[sl]])
         H.call("dcf_camera_mask_points_batch", ctypes.addressof(ptrs), ctypes.addressof(ns), k, H.host_f32(lim), np.ascontiguousarray(crt[sl]),
                float(ulim), float(vlim), int(mode), int(bool(fov)), ctypes.addressof(ms), occ, ctypes.addressof(outs), H.stream_ptr())
     return out_list
@@ -585,26 +616,10 @@ def augment_image_batch(img_u8, params, out=None):
     out: a contiguous uint8 [B,3,H,W] tensor to write into (None = a new one).  It must not overlap the input -- the kernel
     gathers neighbours -- ValueError.  Bit for bit augment_image.transform_image per frame.  One launch per 8 frames.  Returns out."""
     from . import augment_image
-    for name, t in (("img_u8", img_u8), ("out", out)):
-        if t is None and name == "out":
-            continue
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
-            raise H.DcfError("augment_image_batch: %s must be a contiguous uint8 CUDA tensor" % name)
-    if img_u8.dim() != 4 or img_u8.shape[1] != 3 or img_u8.numel() == 0:
-        raise H.DcfError("augment_image_batch: image must be [B,3,H,W] (got %s)" % (tuple(img_u8.shape),))
-    B, _, Hh, Ww = (int(v) for v in img_u8.shape)
-    if len(params) != B:
-        raise H.DcfError("augment_image_batch: %d frames, %d parameter sets" % (B, len(params)))
+    out, B, Hh, Ww = _check_image_pair("augment_image_batch", img_u8, out, len(params), "parameter sets", out_optional=True)
     for p in params:                                 # drawn for another image size: the centre would move
         if (p.get("width", Ww), p.get("height", Hh)) != (Ww, Hh):
             raise H.DcfError("augment_image_batch: parameters of a %d x %d image for a %d x %d one" % (p["width"], p["height"], Ww, Hh))
-    if out is None:
-        out = torch.empty_like(img_u8)
-    if tuple(out.shape) != tuple(img_u8.shape) or out.device != img_u8.device:
-        raise H.DcfError("augment_image_batch: out must be %s on the image's device" % (tuple(img_u8.shape),))
-    nbytes = img_u8.numel()
-    if img_u8.data_ptr() < out.data_ptr() + nbytes and out.data_ptr() < img_u8.data_ptr() + nbytes:
-        raise ValueError("augment_image_batch: out overlaps the input (the kernel gathers neighbouring pixels)")
     for b0 in range(0, B, 8):
         k = min(b0 + 8, B) - b0
         q = np.ascontiguousarray(np.stack([augment_image.vector8(p) for p in params[b0:b0 + k]], 0), dtype=np.float32)
@@ -647,13 +662,11 @@ def paste_points_batch(pts_list, plans, bank_points, out_list):
     B = len(pts_list)
     if len(plans) != B or len(out_list) != B:
         raise H.DcfError("paste_points_batch: %d frames, %d plans, %d outputs" % (B, len(plans), len(out_list)))
-    for t in list(pts_list) + list(out_list) + [bank_points]:
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.is_contiguous() and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == 3):
-            raise H.DcfError("paste_points_batch: frames, outputs and the bank must be contiguous fp32 CUDA tensors [n,3]")
+    _check_point_frames("paste_points_batch", pts_list, out_list, bank=bank_points)
     res = []
     for b0 in range(0, B, 8):
         sl = slice(b0, min(b0 + 8, B))
-        k = sl.stop - sl.start
+        k, ptrs, outs, ns = _chunk_tables(pts_list[sl], out_list[sl], null_by_output=True)
         rec, app = np.zeros((k, 16, 8), dtype=np.float32), np.zeros((k, 16, 2), dtype=np.int64)
         ms = (ctypes.c_int * k)()
         for i, p in enumerate(plans[sl]):
@@ -662,9 +675,6 @@ def paste_points_batch(pts_list, plans, bank_points, out_list):
                 raise H.DcfError("paste_points_batch: a plan holds at most 16 records, one append entry each")
             ms[i] = m
             rec[i, :m], app[i, :m] = p["records"], p["append"]
-        ptrs = (ctypes.c_void_p * k)(*[p.data_ptr() if p.shape[0] else None for p in pts_list[sl]])
-        outs = (ctypes.c_void_p * k)(*[o.data_ptr() if o.shape[0] else None for o in out_list[sl]])
-        ns = (ctypes.c_int * k)(*[int(p.shape[0]) for p in pts_list[sl]])
         caps = (ctypes.c_int * k)(*[int(o.shape[0]) for o in out_list[sl]])
         st = _paste_stage(bank_points.device) if k > PASTE_VALUE_MAX else (None, None)
         H.call("dcf_paste_points_batch", ctypes.addressof(ptrs), ctypes.addressof(ns), k, ctypes.addressof(ms), rec, app,
@@ -682,22 +692,10 @@ def paste_patches_batch(img_u8, plans, bank_patch, out):
     [B,3,H,W] (a view at any byte offset of a larger buffer included), plans = B paste.draw results, bank_patch = the bank's `patch`
     bytes on the device, out = a contiguous uint8 [B,3,H,W] tensor that does not overlap the input (the batch's image is a view of
     the loader's staging set) -- ValueError.  Byte for byte paste.paste_image per frame.  One launch per 8 frames.  Returns out."""
-    for name, t in (("img_u8", img_u8), ("out", out), ("bank_patch", bank_patch)):
-        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
-            raise H.DcfError("paste_patches_batch: %s must be a contiguous uint8 CUDA tensor" % name)
-    if img_u8.dim() != 4 or img_u8.shape[1] != 3 or img_u8.numel() == 0:
-        raise H.DcfError("paste_patches_batch: image must be [B,3,H,W] (got %s)" % (tuple(img_u8.shape),))
-    B, _, Hh, Ww = (int(v) for v in img_u8.shape)
-    if len(plans) != B:
-        raise H.DcfError("paste_patches_batch: %d frames, %d plans" % (B, len(plans)))
+    out, B, Hh, Ww = _check_image_pair("paste_patches_batch", img_u8, out, len(plans), "plans", also=(("bank_patch", bank_patch),))
     for p in plans:                                  # drawn for another image size: the clipping would be another
         if tuple(p.get("image_hw", (Hh, Ww))) != (Hh, Ww):
             raise ValueError("paste_patches_batch: a plan of %s images for %d x %d ones" % (tuple(p["image_hw"]), Hh, Ww))
-    if tuple(out.shape) != tuple(img_u8.shape) or out.device != img_u8.device:
-        raise H.DcfError("paste_patches_batch: out must be %s on the image's device" % (tuple(img_u8.shape),))
-    nbytes = img_u8.numel()
-    if img_u8.data_ptr() < out.data_ptr() + nbytes and out.data_ptr() < img_u8.data_ptr() + nbytes:
-        raise ValueError("paste_patches_batch: out overlaps the input")
     for b0 in range(0, B, 8):
         k = min(b0 + 8, B) - b0
         rec = np.zeros((k, 16, 9), dtype=np.int64)

@@ -4,67 +4,106 @@ Plain Python / numpy, no device: the trainer (train.FlatAdam) evaluates them per
 optimiser kernels by value (csrc/optim.hip, dcf_adamw_ema_step).  The clock of all three is the HOST's count of optimiser
 calls k = 0, 1, 2, ... -- a step the device-side guard skips still advances it, as a torch scheduler stepped beside GradScaler
 does -- so nothing here ever reads the device.
+
+The parsers of the optimiser's other config keys live here too: the guarded step (parse_guard_config) and
+gradient accumulation (parse_accum_config, window_factor, section 17).  All value checks are cfgcheck's.
 """
 import math
 
 import numpy as np
 
+from . import cfgcheck as C
+
 SCHEDULE_KEYS = ("kind", "warmup_steps", "warmup_start_factor", "milestones", "gamma", "total_steps", "min_lr")
 SCHEDULE_KINDS = ("constant", "step", "cosine")
 
 
-def _number(name, v):
-    if isinstance(v, bool) or not isinstance(v, (int, float)):
-        raise ValueError("%s must be a number (got %r)" % (name, v))
-    if not math.isfinite(float(v)):
-        raise ValueError("%s must be finite (got %r)" % (name, v))
-    if v < 0:
-        raise ValueError("%s must not be negative (got %r)" % (name, v))
-    return float(v)
+def parse_guard_config(cfg):
+    """The guarded optimiser step's keys (config_carla.yaml), validated; None = none of them set (the plain Adam step).
+      loss_scale                      none | a positive number (static scale; 1 = the non-finite skip alone) | dynamic
+      loss_scale_init                 first dynamic scale (GradScaler's 65536)
+      loss_scale_growth_factor / loss_scale_backoff_factor / loss_scale_growth_interval    GradScaler's 2.0 / 0.5 / 2000
+      grad_clip_norm                  null | maximum global L2 norm of the averaged, unscaled gradient
+    Bad values raise ValueError.  These keys -- and no others -- take numeric strings (YAML reads 1e4 as one)."""
+    ls = cfg.get("loss_scale", "none")
+    if ls is None or (isinstance(ls, str) and ls.strip().lower() == "none"):
+        mode, scale = None, 1.0
+    elif isinstance(ls, str) and ls.strip().lower() == "dynamic":
+        mode, scale = "dynamic", C.number("loss_scale_init", cfg.get("loss_scale_init", 65536.0), strings=True)
+        if scale <= 0:
+            raise ValueError("loss_scale_init must be positive (got %r)" % (cfg.get("loss_scale_init"),))
+    else:
+        scale = C.number("loss_scale", ls, strings=True)
+        if scale <= 0:
+            raise ValueError("loss_scale must be none, dynamic or a positive number (got %r)" % (ls,))
+        mode = "static"
+    growth = C.number("loss_scale_growth_factor", cfg.get("loss_scale_growth_factor", 2.0), strings=True)
+    backoff = C.number("loss_scale_backoff_factor", cfg.get("loss_scale_backoff_factor", 0.5), strings=True)
+    if growth <= 1.0:
+        raise ValueError("loss_scale_growth_factor must be > 1 (got %r)" % (growth,))
+    if not 0.0 < backoff < 1.0:
+        raise ValueError("loss_scale_backoff_factor must be in (0, 1) (got %r)" % (backoff,))
+    gi = C.integer("loss_scale_growth_interval", cfg.get("loss_scale_growth_interval", 2000), lo=1)
+    clip = cfg.get("grad_clip_norm", None)
+    if clip is not None:
+        clip = C.number("grad_clip_norm", clip, strings=True)
+        if clip <= 0:
+            raise ValueError("grad_clip_norm must be positive or null (got %r)" % (cfg.get("grad_clip_norm"),))
+    if mode is None and clip is None:
+        return None
+    return {"mode": mode, "scale": scale, "growth_factor": growth, "backoff_factor": backoff, "growth_interval": gi,
+            "max_norm": clip}
 
 
-def _count(name, v):
-    if isinstance(v, bool) or not isinstance(v, int):
-        raise ValueError("%s must be an integer (got %r)" % (name, v))
-    if v < 0:
-        raise ValueError("%s must not be negative (got %r)" % (name, v))
-    return int(v)
+def parse_accum_config(cfg):
+    """Gradient accumulation (config_carla.yaml), validated: None = off (grad_accum_steps absent or 1: today's
+    step), else {"steps": k, "reduce": "mean" | "sum"}.
+      grad_accum_steps     k >= 1: one optimiser step per k one_step calls (micro-steps)
+      grad_accum_reduce    mean (default): the optimiser sees (g_1 + ... + g_j) / j over the window's j micro-steps; sum: the plain sum
+    Bad values raise ValueError, whether accumulation is on or not."""
+    k = C.integer("grad_accum_steps", cfg.get("grad_accum_steps", 1), lo=1)
+    red = cfg.get("grad_accum_reduce", "mean")
+    if not isinstance(red, str) or red.strip().lower() not in ("mean", "sum"):
+        raise ValueError("grad_accum_reduce must be mean or sum (got %r)" % (red,))
+    if k == 1:
+        return None
+    return {"steps": k, "reduce": red.strip().lower()}
 
 
-def _flag(name, v):
-    if not isinstance(v, bool):
-        raise ValueError("%s must be true or false (got %r)" % (name, v))
-    return v
+def window_factor(accum, j):
+    """What a window of j micro-steps multiplies into the optimiser's gradient scale: 1 / j under `mean`, 1 under `sum` (and with
+    accumulation off, accum None)."""
+    if accum is None or accum["reduce"] == "sum":
+        return 1.0
+    if isinstance(j, bool) or not isinstance(j, int) or j < 1:
+        raise ValueError("a window holds at least one micro-step (got %r)" % (j,))
+    return 1.0 / j
 
 
 def parse_schedule(blk):
     """The `lr_schedule` block, validated: None (absent) or {"kind", "warmup_steps", "warmup_start_factor", "milestones", "gamma",
-    "total_steps", "min_lr"}."""
+    "total_steps", "min_lr"}.  The recipe's numbers must not be negative."""
     if blk is None:
         return None
-    if not isinstance(blk, dict):
-        raise ValueError("lr_schedule must be a mapping (got %r)" % (blk,))
-    unknown = sorted(set(blk) - set(SCHEDULE_KEYS))
-    if unknown:
-        raise ValueError("lr_schedule: unknown keys %s (known: %s)" % (unknown, list(SCHEDULE_KEYS)))
+    C.block("lr_schedule", blk, SCHEDULE_KEYS)
     kind = blk.get("kind", "constant")
     if kind not in SCHEDULE_KINDS:
         raise ValueError("lr_schedule.kind must be one of %s (got %r)" % (list(SCHEDULE_KINDS), kind))
-    warm = _count("lr_schedule.warmup_steps", blk.get("warmup_steps", 0))
-    f0 = _number("lr_schedule.warmup_start_factor", blk.get("warmup_start_factor", 0.0))
+    warm = C.integer("lr_schedule.warmup_steps", blk.get("warmup_steps", 0), lo=0)
+    f0 = C.number("lr_schedule.warmup_start_factor", blk.get("warmup_start_factor", 0.0), nonneg=True)
     if f0 > 1.0:
         raise ValueError("lr_schedule.warmup_start_factor must be in [0, 1] (got %r)" % (f0,))
     ms = blk.get("milestones", [])
     if not isinstance(ms, (list, tuple)):
         raise ValueError("lr_schedule.milestones must be a list (got %r)" % (ms,))
-    ms = [_count("lr_schedule.milestones", m) for m in ms]
+    ms = [C.integer("lr_schedule.milestones", m, lo=0) for m in ms]
     if any(b < a for a, b in zip(ms, ms[1:])):
         raise ValueError("lr_schedule.milestones must be sorted (got %r)" % (ms,))
-    gamma = _number("lr_schedule.gamma", blk.get("gamma", 0.1))
-    min_lr = _number("lr_schedule.min_lr", blk.get("min_lr", 0.0))
+    gamma = C.number("lr_schedule.gamma", blk.get("gamma", 0.1), nonneg=True)
+    min_lr = C.number("lr_schedule.min_lr", blk.get("min_lr", 0.0), nonneg=True)
     total = blk.get("total_steps", None)
     if total is not None:
-        total = _count("lr_schedule.total_steps", total)
+        total = C.integer("lr_schedule.total_steps", total, lo=0)
     if kind == "cosine":
         if total is None:
             raise ValueError("lr_schedule: kind cosine needs total_steps")
@@ -82,7 +121,7 @@ def parse_optim_config(config):
     Bad values raise ValueError whether or not the feature they belong to is enabled."""
     sched = parse_schedule(config.get("lr_schedule", None))
     wd = config.get("weight_decay", 0.0)
-    wd = 0.0 if wd is None else _number("weight_decay", wd)
+    wd = 0.0 if wd is None else C.number("weight_decay", wd, nonneg=True)
     ex = config.get("weight_decay_exclude", None)
     if ex is None:
         ex = []
@@ -90,11 +129,11 @@ def parse_optim_config(config):
         raise ValueError("weight_decay_exclude must be a list of non-empty strings (got %r)" % (ex,))
     d = config.get("ema_decay", None)
     if d is not None:
-        d = _number("ema_decay", d)
+        d = C.number("ema_decay", d, nonneg=True)
         if d >= 1.0:
             raise ValueError("ema_decay must be in [0, 1) (got %r)" % (d,))
-    warm = _flag("ema_warmup", config.get("ema_warmup", False))
-    ev = _flag("ema_eval", config.get("ema_eval", True))
+    warm = C.flag("ema_warmup", config.get("ema_warmup", False))
+    ev = C.flag("ema_eval", config.get("ema_eval", True))
     if sched is None and wd == 0.0 and d is None:
         return None
     return {"schedule": sched, "weight_decay": wd, "weight_decay_exclude": tuple(ex), "ema_decay": d, "ema_warmup": warm,
@@ -180,18 +219,14 @@ def parse_param_groups(blk, keys=None):
     out = []
     for i, g in enumerate(blk):
         name = "param_groups[%d]" % i
-        if not isinstance(g, dict):
-            raise ValueError("%s must be a mapping (got %r)" % (name, g))
-        unknown = sorted(set(g) - set(GROUP_KEYS))
-        if unknown:
-            raise ValueError("%s: unknown keys %s (known: %s)" % (name, unknown, list(GROUP_KEYS)))
+        C.block(name, g, GROUP_KEYS)
         match = g.get("match", None)
         if not isinstance(match, (list, tuple)) or len(match) == 0 or any(not isinstance(s, str) or not s for s in match):
             raise ValueError("%s.match must be a non-empty list of non-empty strings (got %r)" % (name, match))
-        frozen = _flag(name + ".frozen", g.get("frozen", False))
+        frozen = C.flag(name + ".frozen", g.get("frozen", False))
         if frozen and "lr_mult" in g:
             raise ValueError("%s: frozen and lr_mult exclude each other" % name)
-        mult = _number(name + ".lr_mult", g.get("lr_mult", 1.0))
+        mult = C.number(name + ".lr_mult", g.get("lr_mult", 1.0), nonneg=True)
         out.append({"match": tuple(match), "lr_mult": mult, "frozen": frozen})
     if keys is not None:
         won = set(group_of(k, out) for k in keys)

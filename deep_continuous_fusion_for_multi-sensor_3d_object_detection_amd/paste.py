@@ -21,6 +21,7 @@ import math
 
 import numpy as np
 
+from . import cfgcheck as C
 from .augment import M64, mix64
 
 MAX_RECORDS = 16           # records per frame: the kernels' table holds 16
@@ -176,14 +177,33 @@ def destination(rect, centre_px, row, crt, image_hw, here=False):
 
 # ------------------------------------------------------------------------------------------------ the sampler
 def check_config(cfg):
-    """Range checks of the parsed block (train.parse_paste_config's dict, or any dict with those keys): ValueError."""
-    t, c, m = cfg.get("target_objects", 15), cfg.get("max_candidates", 16), cfg.get("margin", 0.0)
-    if isinstance(t, bool) or not isinstance(t, int) or t < 0:
-        raise ValueError("augment_paste.target_objects must be an integer >= 0 (got %r)" % (t,))
-    if isinstance(c, bool) or not isinstance(c, int) or not 1 <= c <= MAX_RECORDS:
-        raise ValueError("augment_paste.max_candidates must be an integer in 1..%d (got %r)" % (MAX_RECORDS, c))
-    if isinstance(m, bool) or not isinstance(m, (int, float)) or not (math.isfinite(float(m)) and float(m) >= 0.0):
-        raise ValueError("augment_paste.margin must be a finite number >= 0 (got %r)" % (m,))
+    """Range checks of the parsed block (parse_config's dict, or any dict with those keys): ValueError."""
+    C.integer("augment_paste.target_objects", cfg.get("target_objects", 15), lo=0)
+    C.integer("augment_paste.max_candidates", cfg.get("max_candidates", 16), lo=1, hi=MAX_RECORDS)
+    C.number("augment_paste.margin", cfg.get("margin", 0.0), nonneg=True)
+
+
+def parse_config(config):
+    """The `augment_paste` block, validated like `augment`: None = off (no block, or enabled: false), else
+    {"seed", "bank" (path of the .npz), "target_objects", "max_candidates" (1..16), "margin" (metres, >= 0), "paste_image"}.  Bad
+    values raise ValueError whether the block is enabled or not; an enabled block needs a bank."""
+    got = C.seeded_block(config, "augment_paste", KEYS)
+    if got is None:
+        return None
+    blk, enabled, seed = got
+    with_image = C.flag("augment_paste.paste_image", blk.get("paste_image", True))
+    bank = blk.get("bank", None)
+    if bank is not None and not isinstance(bank, str):
+        raise ValueError("augment_paste.bank must be the path of an object bank (got %r)" % (bank,))
+    out = {"seed": seed, "bank": bank, "target_objects": blk.get("target_objects", 15), "max_candidates": blk.get("max_candidates", 16),
+           "margin": blk.get("margin", 0.0), "paste_image": with_image}
+    check_config(out)
+    out["margin"] = float(out["margin"])
+    if not enabled:
+        return None
+    if not bank:
+        raise ValueError("augment_paste.bank: an enabled block needs the path of an object bank (python -m <package>.objbank --out PATH)")
+    return out
 
 
 def check_bank(bank, image_hw=None):
@@ -208,7 +228,7 @@ def empty_plan(n_points, image_hw):
 
 
 def draw(cfg, seed, rank, call, b, bank, boxes, num, n_points, crt, config):
-    """The plan of frame b of the call-th augmented step on `rank`.  cfg: the dict of train.parse_paste_config; bank: objbank's
+    """The plan of frame b of the call-th augmented step on `rank`.  cfg: the dict of parse_config; bank: objbank's
     dict; boxes [max_num_bbox, 9] with the first `num` rows valid, n_points and crt [4,3]: the frame's own labels, point count
     and calibration; config: the dataset config (ranges, max_num_bbox, max_num_pc).
 

@@ -12,252 +12,27 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
+from . import augment as AUG
+from . import augment_image as AUGI
 from . import ops
 from . import optim as OPT
+from . import paste as PST
+from . import visibility as VIS
 from .loss import LossTotal
 from ._hip import torch_dtype as H_torch_dtype
 from .model import ObjectDetection_DCF, parse_deterministic_config
-
-
-def parse_guard_config(cfg):
-    """The guarded optimiser step's keys (config_carla.yaml), validated; None = none of them set (the plain Adam step).
-      loss_scale                      none | a positive number (static scale; 1 = the non-finite skip alone) | dynamic
-      loss_scale_init                 first dynamic scale (GradScaler's 65536)
-      loss_scale_growth_factor / loss_scale_backoff_factor / loss_scale_growth_interval    GradScaler's 2.0 / 0.5 / 2000
-      grad_clip_norm                  null | maximum global L2 norm of the averaged, unscaled gradient
-    Bad values raise ValueError."""
-    import math
-
-    def number(key, default):
-        v = cfg.get(key, default)
-        if isinstance(v, bool):
-            raise ValueError("%s must be a number (got %r)" % (key, v))
-        try:
-            f = float(v)
-        except (TypeError, ValueError):
-            raise ValueError("%s must be a number (got %r)" % (key, v))
-        if not math.isfinite(f):
-            raise ValueError("%s must be finite (got %r)" % (key, v))
-        return f
-
-    ls = cfg.get("loss_scale", "none")
-    if ls is None or (isinstance(ls, str) and ls.strip().lower() == "none"):
-        mode, scale = None, 1.0
-    elif isinstance(ls, str) and ls.strip().lower() == "dynamic":
-        mode, scale = "dynamic", number("loss_scale_init", 65536.0)
-        if scale <= 0:
-            raise ValueError("loss_scale_init must be positive (got %r)" % (cfg.get("loss_scale_init"),))
-    else:
-        scale = number("loss_scale", None)
-        if scale <= 0:
-            raise ValueError("loss_scale must be none, dynamic or a positive number (got %r)" % (ls,))
-        mode = "static"
-    growth = number("loss_scale_growth_factor", 2.0)
-    backoff = number("loss_scale_backoff_factor", 0.5)
-    if growth <= 1.0:
-        raise ValueError("loss_scale_growth_factor must be > 1 (got %r)" % (growth,))
-    if not 0.0 < backoff < 1.0:
-        raise ValueError("loss_scale_backoff_factor must be in (0, 1) (got %r)" % (backoff,))
-    gi = cfg.get("loss_scale_growth_interval", 2000)
-    if isinstance(gi, bool) or not isinstance(gi, int) or gi < 1:
-        raise ValueError("loss_scale_growth_interval must be a positive integer (got %r)" % (gi,))
-    clip = cfg.get("grad_clip_norm", None)
-    if clip is not None:
-        clip = number("grad_clip_norm", None)
-        if clip <= 0:
-            raise ValueError("grad_clip_norm must be positive or null (got %r)" % (cfg.get("grad_clip_norm"),))
-    if mode is None and clip is None:
-        return None
-    return {"mode": mode, "scale": scale, "growth_factor": growth, "backoff_factor": backoff, "growth_interval": gi,
-            "max_norm": clip}
-
-
-def parse_accum_config(cfg):
-    """Gradient accumulation (config_carla.yaml), validated: None = off (grad_accum_steps absent or 1: today's
-    step), else {"steps": k, "reduce": "mean" | "sum"}.
-      grad_accum_steps     k >= 1: one optimiser step per k one_step calls (micro-steps)
-      grad_accum_reduce    mean (default): the optimiser sees (g_1 + ... + g_j) / j over the window's j micro-steps; sum: the plain sum
-    Bad values raise ValueError, whether accumulation is on or not."""
-    k = cfg.get("grad_accum_steps", 1)
-    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
-        raise ValueError("grad_accum_steps must be an integer >= 1 (got %r)" % (k,))
-    red = cfg.get("grad_accum_reduce", "mean")
-    if not isinstance(red, str) or red.strip().lower() not in ("mean", "sum"):
-        raise ValueError("grad_accum_reduce must be mean or sum (got %r)" % (red,))
-    if k == 1:
-        return None
-    return {"steps": int(k), "reduce": red.strip().lower()}
-
-
-def window_factor(accum, j):
-    """What a window of j micro-steps multiplies into the optimiser's gradient scale: 1 / j under `mean`, 1 under `sum` (and with
-    accumulation off, accum None)."""
-    if accum is None or accum["reduce"] == "sum":
-        return 1.0
-    if isinstance(j, bool) or not isinstance(j, int) or j < 1:
-        raise ValueError("a window holds at least one micro-step (got %r)" % (j,))
-    return 1.0 / j
-
-
-AUGMENT_KEYS = ("enabled", "seed", "rotation_deg", "scale", "flip_prob", "point_drop")
-
-
-def parse_augment_config(config):
-    """The `augment` block (config_carla.yaml; augment.py), validated: None = off (no block, or enabled:
-    false), else {"seed", "rotation_deg", "scale": (lo, hi), "flip_prob", "point_drop": (lo, hi)}.  Bad values raise ValueError
-    whether the block is enabled or not -- augmentation is never switched off quietly."""
-    import math
-    blk = config.get("augment", None)
-    if blk is None:
-        return None
-    if not isinstance(blk, dict):
-        raise ValueError("augment must be a mapping (got %r)" % (blk,))
-    unknown = sorted(set(blk) - set(AUGMENT_KEYS))
-    if unknown:
-        raise ValueError("augment: unknown keys %s (known: %s)" % (unknown, list(AUGMENT_KEYS)))
-
-    def number(key, v):
-        if isinstance(v, bool) or not isinstance(v, (int, float)):
-            raise ValueError("augment.%s must be a number (got %r)" % (key, v))
-        if not math.isfinite(float(v)):
-            raise ValueError("augment.%s must be finite (got %r)" % (key, v))
-        return float(v)
-
-    def interval(key, default):
-        v = blk.get(key, default)
-        if not isinstance(v, (list, tuple)) or len(v) != 2:
-            raise ValueError("augment.%s must be [lo, hi] (got %r)" % (key, v))
-        lo, hi = number(key, v[0]), number(key, v[1])
-        if lo > hi:
-            raise ValueError("augment.%s: lo > hi (got %r)" % (key, v))
-        return lo, hi
-
-    def probability(key, v):
-        if not 0.0 <= v <= 1.0:
-            raise ValueError("augment.%s must be a probability in [0, 1] (got %r)" % (key, v))
-        return v
-
-    enabled = blk.get("enabled", False)
-    if not isinstance(enabled, bool):
-        raise ValueError("augment.enabled must be true or false (got %r)" % (enabled,))
-    seed = blk.get("seed", 0)
-    if isinstance(seed, bool) or not isinstance(seed, int):
-        raise ValueError("augment.seed must be an integer (got %r)" % (seed,))
-    rot = number("rotation_deg", blk.get("rotation_deg", 0.0))
-    if rot < 0.0:
-        raise ValueError("augment.rotation_deg: theta ~ U(-r, +r) needs r >= 0 (got %r)" % (rot,))
-    scale = interval("scale", (1.0, 1.0))
-    if scale[0] <= 0.0:
-        raise ValueError("augment.scale must be positive (got %r)" % (blk.get("scale"),))
-    flip = probability("flip_prob", number("flip_prob", blk.get("flip_prob", 0.0)))
-    drop = interval("point_drop", (0.0, 0.0))
-    probability("point_drop", drop[0])
-    probability("point_drop", drop[1])
-    if not enabled:
-        return None
-    return {"seed": int(seed), "rotation_deg": rot, "scale": scale, "flip_prob": flip, "point_drop": drop}
-
-
-IMAGE_AUGMENT_KEYS = ("enabled", "seed", "zoom", "shift", "flip_prob", "brightness", "contrast", "channel_gain", "drop_prob")
-
-
-def parse_image_augment_config(config):
-    """The `augment_image` block (augment_image.py), validated like `augment`: None = off (no block, or
-    enabled: false), else {"seed", "zoom": (lo, hi), "shift": (fx, fy), "flip_prob", "brightness": (lo, hi), "contrast": (lo, hi),
-    "channel_gain": (lo, hi), "drop_prob"}.  Bad values raise ValueError whether the block is enabled or not.  zoom needs
-    lo >= 0.5: the two-tap bilinear of the kernel covers every source pixel only up to a 2x minification (a bound derived from
-    the filter's footprint, not a measured one)."""
-    import math
-    blk = config.get("augment_image", None)
-    if blk is None:
-        return None
-    if not isinstance(blk, dict):
-        raise ValueError("augment_image must be a mapping (got %r)" % (blk,))
-    unknown = sorted(set(blk) - set(IMAGE_AUGMENT_KEYS))
-    if unknown:
-        raise ValueError("augment_image: unknown keys %s (known: %s)" % (unknown, list(IMAGE_AUGMENT_KEYS)))
-
-    def number(key, v):
-        if isinstance(v, bool) or not isinstance(v, (int, float)):
-            raise ValueError("augment_image.%s must be a number (got %r)" % (key, v))
-        if not math.isfinite(float(v)):
-            raise ValueError("augment_image.%s must be finite (got %r)" % (key, v))
-        return float(v)
-
-    def pair(key, default):
-        v = blk.get(key, default)
-        if not isinstance(v, (list, tuple)) or len(v) != 2:
-            raise ValueError("augment_image.%s must be a pair (got %r)" % (key, v))
-        return number(key, v[0]), number(key, v[1])
-
-    def interval(key, least=None):
-        lo, hi = pair(key, (1.0, 1.0))
-        if lo > hi:
-            raise ValueError("augment_image.%s: lo > hi (got %r)" % (key, blk.get(key)))
-        if lo <= 0.0 or (least is not None and lo < least):
-            raise ValueError("augment_image.%s must be %s (got %r)" % (key, "positive" if least is None else ">= %g" % least, blk.get(key)))
-        return lo, hi
-
-    def probability(key):
-        v = number(key, blk.get(key, 0.0))
-        if not 0.0 <= v <= 1.0:
-            raise ValueError("augment_image.%s must be a probability in [0, 1] (got %r)" % (key, v))
-        return v
-
-    enabled = blk.get("enabled", False)
-    if not isinstance(enabled, bool):
-        raise ValueError("augment_image.enabled must be true or false (got %r)" % (enabled,))
-    seed = blk.get("seed", 0)
-    if isinstance(seed, bool) or not isinstance(seed, int):
-        raise ValueError("augment_image.seed must be an integer (got %r)" % (seed,))
-    zoom = interval("zoom", least=0.5)
-    shift = pair("shift", (0.0, 0.0))
-    if not (0.0 <= shift[0] <= 0.5 and 0.0 <= shift[1] <= 0.5):
-        raise ValueError("augment_image.shift: fractions of the width and height in [0, 0.5] (got %r)" % (blk.get("shift"),))
-    out = {"seed": int(seed), "zoom": zoom, "shift": shift, "flip_prob": probability("flip_prob"), "brightness": interval("brightness"),
-           "contrast": interval("contrast"), "channel_gain": interval("channel_gain"), "drop_prob": probability("drop_prob")}
-    return out if enabled else None
-
-
-def parse_paste_config(config):
-    """The `augment_paste` block (paste.py), validated like the other two: None = off (no block, or
-    enabled: false), else {"seed", "bank" (path of the .npz), "target_objects", "max_candidates" (1..16), "margin" (metres, >= 0),
-    "paste_image"}.  Bad values raise ValueError whether the block is enabled or not; an enabled block needs a bank."""
-    from . import paste as PST
-    blk = config.get("augment_paste", None)
-    if blk is None:
-        return None
-    if not isinstance(blk, dict):
-        raise ValueError("augment_paste must be a mapping (got %r)" % (blk,))
-    unknown = sorted(set(blk) - set(PST.KEYS))
-    if unknown:
-        raise ValueError("augment_paste: unknown keys %s (known: %s)" % (unknown, list(PST.KEYS)))
-    enabled, with_image = blk.get("enabled", False), blk.get("paste_image", True)
-    for key, v in (("enabled", enabled), ("paste_image", with_image)):
-        if not isinstance(v, bool):
-            raise ValueError("augment_paste.%s must be true or false (got %r)" % (key, v))
-    seed = blk.get("seed", 0)
-    if isinstance(seed, bool) or not isinstance(seed, int):
-        raise ValueError("augment_paste.seed must be an integer (got %r)" % (seed,))
-    bank = blk.get("bank", None)
-    if bank is not None and not isinstance(bank, str):
-        raise ValueError("augment_paste.bank must be the path of an object bank (got %r)" % (bank,))
-    out = {"seed": int(seed), "bank": bank, "target_objects": blk.get("target_objects", 15), "max_candidates": blk.get("max_candidates", 16),
-           "margin": blk.get("margin", 0.0), "paste_image": with_image}
-    PST.check_config(out)
-    out["margin"] = float(out["margin"])
-    if not enabled:
-        return None
-    if not bank:
-        raise ValueError("augment_paste.bank: an enabled block needs the path of an object bank (python -m <package>.objbank --out PATH)")
-    return out
+from .calib import own_crts
+# every block's parser lives beside its feature; the names stay importable from here
+from .augment import KEYS as AUGMENT_KEYS, parse_config as parse_augment_config
+from .augment_image import KEYS as IMAGE_AUGMENT_KEYS, parse_config as parse_image_augment_config
+from .optim import parse_accum_config, parse_guard_config, window_factor
+from .paste import parse_config as parse_paste_config
 
 
 def parse_camera_mask_config(config):
     """The `camera_mask` block (visibility.py): None = off (no block, or both switches false: no buffer, no
     launch), else {"fov_crop", "paste_occlusion"}.  Unknown keys and non-boolean values raise ValueError, and so does
     paste_occlusion: true without an enabled augment_paste block with paste_image: true -- the occluders are the painted patches."""
-    from . import visibility as VIS
     out = VIS.parse_config(config)
     if out is not None and out["paste_occlusion"]:
         pst = parse_paste_config(config)
@@ -272,7 +47,6 @@ def draw_paste_plans(cfg, bank, rank, call, boxes, nums, n_points, crts, config,
     they came.  dropped (camera_mask.paste_occlusion): a list; every plan then goes through visibility.drop_covering before its labels
     are appended -- a candidate whose patch would be painted over a nearer label of the frame is not pasted -- and the list
     receives the number of objects each frame lost."""
-    from . import paste as PST
     src = np.asarray(boxes, dtype=np.float32)
     cnt = [int(v) for v in np.asarray(nums).reshape(-1)]
     hw = (int(config["image_height"]), int(config["image_width"])) if bank is None else bank["image_hw"]
@@ -280,7 +54,6 @@ def draw_paste_plans(cfg, bank, rank, call, boxes, nums, n_points, crts, config,
         return [PST.empty_plan(n_points[b], hw) for b in range(len(cnt))], src, cnt
     plans = [PST.draw(cfg, cfg["seed"], rank, call, b, bank, src[b], cnt[b], n_points[b], crts[b], config) for b in range(len(cnt))]
     if dropped is not None:
-        from . import visibility as VIS
         drawn = plans
         plans = [VIS.drop_covering(drawn[b], src[b], cnt[b], crts[b], bank) for b in range(len(cnt))]
         dropped.extend(len(d["rows"]) - len(p["rows"]) for d, p in zip(drawn, plans))
@@ -367,10 +140,7 @@ class FlatAdam(object):
         if self.groups is not None:
             return self._step_groups(lr, gscale, omd)
         if self.amp is not None:
-            g = self.guard
-            ops.grad_stats(self.model.flat_grads, self.amp)
-            ops.amp_update(self.amp, gscale, g["mode"] == "dynamic", g["growth_factor"], g["backoff_factor"], g["growth_interval"],
-                           g["max_norm"], lr, self.betas[0], self.betas[1])
+            self._guard_scan(lr, gscale)
             if self.fused:
                 ops.adamw_ema_step(self.model.flat_params, self.model.flat_grads, self.m, self.v, lr, self.betas[0], self.betas[1],
                                    self.eps, 0, gscale, decay_mul, self.decay_bits, self.ema, omd, self.amp)
@@ -386,16 +156,21 @@ class FlatAdam(object):
             ops.adam_step(self.model.flat_params, self.model.flat_grads, self.m, self.v, lr, self.betas[0], self.betas[1],
                           self.eps, self._step_count, gscale)
 
+    def _guard_scan(self, lr, gscale):
+        """The guarded step's two launches in front of the Adam pass: the scan of the gradient arena, then the device-side decision
+        (skip, clip factor, next loss scale)."""
+        g = self.guard
+        ops.grad_stats(self.model.flat_grads, self.amp)
+        ops.amp_update(self.amp, gscale, g["mode"] == "dynamic", g["growth_factor"], g["backoff_factor"], g["growth_interval"],
+                       g["max_norm"], lr, self.betas[0], self.betas[1])
+
     def _step_groups(self, lr, gscale, omd):
         """step() with param_groups: the guard's scan and norm run over the WHOLE arena (a frozen tensor whose gradient the backward
         still computes counts; the frozen trunk prefix contributes exact zeros), then the one grouped pass."""
         wd = self.recipe["weight_decay"] if self.recipe is not None else 0.0
         table = OPT.group_table(self.groups, lr, wd)
         if self.amp is not None:
-            g = self.guard
-            ops.grad_stats(self.model.flat_grads, self.amp)
-            ops.amp_update(self.amp, gscale, g["mode"] == "dynamic", g["growth_factor"], g["backoff_factor"], g["growth_interval"],
-                           g["max_norm"], lr, self.betas[0], self.betas[1])
+            self._guard_scan(lr, gscale)
             step = 0
         else:
             self._step_count += 1
@@ -424,6 +199,10 @@ class FlatAdam(object):
 
 def world():
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+
+
+def this_rank():
+    return dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
 
 
 def _through_host(t):
@@ -526,7 +305,7 @@ class Train(nn.Module):
         self._paste_bank, self._paste_dev, self._paste_image_buf = None, None, None
         self.last_paste = []
         if self.paste is not None:
-            from . import objbank, paste as PST
+            from . import objbank
             try:
                 self._paste_bank = objbank.load(self.paste["bank"])
             except OSError as e:
@@ -637,40 +416,7 @@ class Train(nn.Module):
             st["used"] = True
         with torch.cuda.stream(self._side):
             pcs, uvs, cnts = [], [], []
-            if paste is not None:
-                if len(paste) != Bn:
-                    raise ValueError("paste: %d plans for %d frames" % (len(paste), Bn))
-                if self._paste_dev is None:
-                    raise ValueError("paste: the trainer was built without an object bank (augment_paste)")
-                src = [frame_geometry._pts(p) for p in points_list]
-                rows = [int(p.shape[0]) + int(q["append"][:, 1].sum()) for p, q in zip(src, paste)]
-                if st is not None and max(rows) <= mp:  # fixed addresses, as the augmented points below
-                    if "paste" not in st:
-                        st["paste"] = torch.empty((Bn, mp, 3), dtype=torch.float32, device=src[0].device)
-                    dst = [st["paste"][b] for b in range(Bn)]
-                else:
-                    dst = [torch.empty((r, 3), dtype=torch.float32, device=src[0].device) for r in rows]
-                points_list = ops.paste_points_batch(src, list(paste), self._paste_dev[0], dst)
-            if self.camera_mask is not None:
-                points_list = self._camera_mask_points(frame_geometry, points_list, crts, paste, st, mp)
-            if augment is not None:
-                from . import augment as AUG
-                if len(augment) != Bn:
-                    raise ValueError("augment: %d parameter sets for %d frames" % (len(augment), Bn))
-                src = [frame_geometry._pts(p) for p in points_list]
-                if st is not None:                      # fixed addresses; a frame over max_num_pc takes the allocating path
-                    if "aug" not in st:
-                        st["aug"] = torch.empty((Bn, mp, 3), dtype=torch.float32, device=src[0].device)
-                    dst = [st["aug"][b, :p.shape[0]] for b, p in enumerate(src)]
-                else:
-                    dst = [torch.empty_like(p) for p in src]
-                points_list = ops.augment_points_batch(src, list(augment), dst)
-                crts = [AUG.compose_crt(frame_geometry.crt if (crts is None or crts[b] is None) else crts[b], augment[b]) for b in range(Bn)]
-            if image_augment is not None:
-                from . import augment_image as AUGI
-                if len(image_augment) != Bn:
-                    raise ValueError("image_augment: %d parameter sets for %d frames" % (len(image_augment), Bn))
-                crts = [AUGI.compose_crt_image(frame_geometry.crt if (crts is None or crts[b] is None) else crts[b], image_augment[b]) for b in range(Bn)]
+            points_list, crts = self._point_stages(frame_geometry, points_list, crts, st, mp, paste, augment, image_augment)
             if st is not None:
                 x_lidar = st["x_lidar"]
                 st["proj"].zero_()
@@ -733,15 +479,51 @@ class Train(nn.Module):
                     t.record_stream(main)
         return x_lidar, geom
 
+    @staticmethod
+    def _stage_buffers(st, name, src, mp, rows=None):
+        """Where a point stage writes the frames `src`: views of the geometry set's persistent [B, max_num_pc, 3] buffer st[name] --
+        fixed addresses; allocated on first use, under the caller's side-stream context (the comment in geometry_async says why)
+        -- or, without a set (a frame over max_num_pc), new tensors.  rows None (mask, augment): frame b gets [b, :n_b] of the
+        buffer, or a tensor like src[b].  rows (paste, whose frames grow to rows[b]): whole [b] rows of the buffer, and only when
+        max(rows) <= max_num_pc, else tensors of rows[b] rows -- the row count of an output is the capacity the kernel is told."""
+        if st is None or (rows is not None and max(rows) > mp):
+            return [torch.empty((p.shape[0] if rows is None else rows[b], 3), dtype=torch.float32, device=p.device) for b, p in enumerate(src)]
+        if name not in st:
+            st[name] = torch.empty((len(src), mp, 3), dtype=torch.float32, device=src[0].device)
+        return [st[name][b] if rows is not None else st[name][b, :p.shape[0]] for b, p in enumerate(src)]
+
+    def _point_stages(self, frame_geometry, points_list, crts, st, mp, paste, augment, image_augment):
+        """The point stages of geometry_async, on the side stream in front of the projection: paste, then the camera mask, then the
+        BEV transform, each reading what the one before wrote; and the projection matrices under the two augmentations.  Returns
+        (points_list, crts)."""
+        Bn = len(points_list)
+        for name, per_frame in (("paste", paste), ("augment", augment), ("image_augment", image_augment)):
+            if per_frame is not None and len(per_frame) != Bn:
+                raise ValueError("%s: %d %s for %d frames" % (name, len(per_frame), "plans" if name == "paste" else "parameter sets", Bn))
+        if paste is not None:
+            if self._paste_dev is None:
+                raise ValueError("paste: the trainer was built without an object bank (augment_paste)")
+            src = [frame_geometry._pts(p) for p in points_list]
+            rows = [int(p.shape[0]) + int(q["append"][:, 1].sum()) for p, q in zip(src, paste)]
+            points_list = ops.paste_points_batch(src, list(paste), self._paste_dev[0], self._stage_buffers(st, "paste", src, mp, rows))
+        if self.camera_mask is not None:
+            points_list = self._camera_mask_points(frame_geometry, points_list, crts, paste, st, mp)
+        if augment is not None:
+            src = [frame_geometry._pts(p) for p in points_list]
+            points_list = ops.augment_points_batch(src, list(augment), self._stage_buffers(st, "aug", src, mp))
+            crts = [AUG.compose_crt(m, q) for m, q in zip(own_crts(frame_geometry.crt, crts, Bn), augment)]
+        if image_augment is not None:
+            crts = [AUGI.compose_crt_image(m, q) for m, q in zip(own_crts(frame_geometry.crt, crts, Bn), image_augment)]
+        return points_list, crts
+
     def _camera_mask_points(self, frame_geometry, points_list, crts, paste, st, mp):
         """The camera visibility mask of geometry_async, on the side stream behind the paste launch and in
         front of `augment`: every frame under its OWN, un-augmented matrix -- augment.compose_crt keeps every point on the pixel of
         its original, so the decision holds under the BEV and image blocks.  Pasted frames (buffers of this call) are masked in
         place; the loader's staging views are never written: their masked copy goes to a persistent [B, max_num_pc, 3] buffer of
         the geometry set, or -- a frame over max_num_pc, as for `augment` -- to new tensors."""
-        from . import visibility as VIS
         cm, Bn = self.camera_mask, len(points_list)
-        own = [frame_geometry.crt if (crts is None or crts[b] is None) else crts[b] for b in range(Bn)]
+        own = own_crts(frame_geometry.crt, crts, Bn)
         occ = None
         if cm["paste_occlusion"] and paste is not None:
             occ = [VIS.occluders(paste[b], self._paste_bank, own[b]) for b in range(Bn)]
@@ -750,14 +532,7 @@ class Train(nn.Module):
         if not cm["fov_crop"] and occ is None:
             return points_list
         src = [frame_geometry._pts(p) for p in points_list]
-        if paste is not None:
-            dst = src
-        elif st is not None:
-            if "mask" not in st:
-                st["mask"] = torch.empty((Bn, mp, 3), dtype=torch.float32, device=src[0].device)
-            dst = [st["mask"][b, :p.shape[0]] for b, p in enumerate(src)]
-        else:
-            dst = None
+        dst = src if paste is not None else (None if st is None else self._stage_buffers(st, "mask", src, mp))
         return frame_geometry.mask_points(src, own, cm["fov_crop"], occ, out=dst)
 
     def _predict(self, lidar_voxel, camera_image, extra):
@@ -891,56 +666,40 @@ class Train(nn.Module):
         self.optimizer.step((1.0 / n) * window_factor(self.accum, j))
 
     def one_step_raw(self, frame_geometry, batch):
-        """One train step from a FrameLoader batch (raw points + image in HBM): geometry on the side stream, then one_step."""
+        """One train step from a FrameLoader batch (raw points + image in HBM): the sample pipeline, geometry on the side stream, then
+        one_step.  Every block of the pipeline is one `if`; all of them draw at the step's one call count, which ticks once when any
+        of them drew (the camera mask draws nothing).  Everything is pasted in the un-augmented frame: the
+        labels get the pasted rows before augment.transform_boxes moves them, the side stream writes the pasted points in front of
+        the mask and the BEV transform, and the patches are painted (compute stream) in front of the image transform."""
         batch.wait()
-        boxes, nums, params = batch["bboxes"], batch["num_bboxes"], None
+        call = self.aug_calls
+        points, crts, image = batch["points"], batch.get("crt"), batch["image"]
+        boxes, nums, plans, params, iparams = batch["bboxes"], batch["num_bboxes"], None, None, None
         if self.paste is not None:
-            return self._one_step_raw_paste(frame_geometry, batch)
-        if self.image_augment is None:             # the step as it is without the image block
-            if self.augment is not None:
-                params, boxes, nums = self._draw_augment(frame_geometry, boxes, nums)
-            x_lidar, geom = self.geometry_async(frame_geometry, batch["points"], crts=batch.get("crt"), wait_event=batch.event, augment=params)
-            self.one_step(x_lidar, batch["image"], boxes, nums, geom=geom)
-            return
-        # both blocks draw from the same call count, which ticks once per step
-        call = self.aug_calls
+            plans, boxes, nums = self._draw_paste(frame_geometry, points, crts, boxes, nums, call)
         if self.augment is not None:
-            params, boxes, nums = self._draw_augment(frame_geometry, boxes, nums)
-        self.aug_calls = call + 1
-        image, iparams = self._augment_image(batch["image"], call)
-        x_lidar, geom = self.geometry_async(frame_geometry, batch["points"], crts=batch.get("crt"), wait_event=batch.event, augment=params,
-                                            image_augment=iparams)
-        self.one_step(x_lidar, image, boxes, nums, geom=geom)
-
-    def _one_step_raw_paste(self, frame_geometry, batch):
-        """one_step_raw with the paste block on: paste, then `augment`, then `augment_image`, every block drawn
-        at the step's one call count, which ticks once.  Everything is pasted in the un-augmented frame: the labels get the pasted
-        rows before augment.transform_boxes moves them, the side stream writes the pasted points in front of the BEV transform, and
-        the patches are painted (compute stream, one persistent buffer) in front of the image transform."""
-        call = self.aug_calls
-        boxes, nums, params, iparams = batch["bboxes"], batch["num_bboxes"], None, None
-        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
-        points, crts = batch["points"], batch.get("crt")
-        own = [frame_geometry.crt if (crts is None or crts[b] is None) else crts[b] for b in range(len(points))]
-        dropped = [] if (self.camera_mask is not None and self.camera_mask["paste_occlusion"]) else None
-        plans, new_boxes, new_nums = draw_paste_plans(self.paste, self._paste_bank, rank, call, boxes.detach().cpu().numpy(), torch.as_tensor(nums).numpy(),
-                                                      [int(p.shape[0]) for p in points], own, frame_geometry.config, dropped=dropped)
-        self.last_paste = [list(p["rows"]) for p in plans]
-        if dropped is not None:
-            self.last_masked = [(len(p["patches"]), d) for p, d in zip(plans, dropped)]
-        boxes = torch.from_numpy(new_boxes).to(boxes.dtype)
-        nums = torch.tensor(new_nums, dtype=torch.as_tensor(nums).dtype)
-        if self.augment is not None:               # (draws at aug_calls == call and counts it)
-            params, boxes, nums = self._draw_augment(frame_geometry, boxes, nums)
-        self.aug_calls = call + 1
-        image = batch["image"]
-        if self.paste["paste_image"]:
+            params, boxes, nums = self._draw_augment(frame_geometry, boxes, nums, call)
+        if self.paste is not None and self.paste["paste_image"]:
             image = self._paste_image(image, plans)
         if self.image_augment is not None:
             image, iparams = self._augment_image(image, call)
+        if not (plans is None and params is None and iparams is None):
+            self.aug_calls = call + 1
         x_lidar, geom = self.geometry_async(frame_geometry, points, crts=crts, wait_event=batch.event, augment=params, image_augment=iparams,
                                             paste=plans)
         self.one_step(x_lidar, image, boxes, nums, geom=geom)
+
+    def _draw_paste(self, frame_geometry, points, crts, boxes, nums, call):
+        """This step's per-frame paste plans (draw_paste_plans at `call`, every frame under its own matrix) and the labels with the
+        pasted rows appended (host tensors); last_paste / last_masked keep what the logs print."""
+        dropped = [] if (self.camera_mask is not None and self.camera_mask["paste_occlusion"]) else None
+        plans, new_boxes, new_nums = draw_paste_plans(self.paste, self._paste_bank, this_rank(), call, boxes.detach().cpu().numpy(),
+                                                      torch.as_tensor(nums).numpy(), [int(p.shape[0]) for p in points],
+                                                      own_crts(frame_geometry.crt, crts, len(points)), frame_geometry.config, dropped=dropped)
+        self.last_paste = [list(p["rows"]) for p in plans]
+        if dropped is not None:
+            self.last_masked = [(len(p["patches"]), d) for p, d in zip(plans, dropped)]
+        return plans, torch.from_numpy(new_boxes).to(boxes.dtype), torch.tensor(new_nums, dtype=torch.as_tensor(nums).dtype)
 
     def _paste_image(self, image, plans):
         """The batch's uint8 [B,3,H,W] image with this step's patches painted in: one launch on the compute stream -- the stream of
@@ -961,26 +720,21 @@ class Train(nn.Module):
         on the compute stream -- the stream of its consumer, so no events -- into the trainer's one persistent buffer (allocated
         on first use, re-made when the shape changes).  Outside the captured graphs: a replay copies it into its static image
         buffer as it does any image."""
-        from . import augment_image as AUGI
         if image.dtype != torch.uint8 or image.dim() != 4 or not image.is_cuda:
             raise ValueError("augment_image needs the batch's image as a uint8 [B,3,H,W] device tensor (got %s %s)" % (image.dtype, tuple(image.shape)))
-        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
         Bn, _, Hh, Ww = (int(v) for v in image.shape)
-        cfg = self.image_augment
+        cfg, rank = self.image_augment, this_rank()
         iparams = [AUGI.draw(cfg, cfg["seed"], rank, call, b, Ww, Hh) for b in range(Bn)]
         if self._aug_image is None or self._aug_image.shape != image.shape or self._aug_image.device != image.device:
             self._aug_image = torch.empty(tuple(image.shape), dtype=torch.uint8, device=image.device)
         ops.augment_image_batch(image.contiguous(), iparams, self._aug_image)
         return self._aug_image, iparams
 
-    def _draw_augment(self, frame_geometry, boxes, nums):
-        """This step's per-frame augmentation parameters and the labels under them (host tensors of max_num_bbox rows: no device
-        read, no synchronisation); counts the call."""
-        from . import augment as AUG
-        rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
-        Bn = int(boxes.shape[0])
-        params = [AUG.draw(self.augment, self.augment["seed"], rank, self.aug_calls, b) for b in range(Bn)]
-        self.aug_calls += 1
+    def _draw_augment(self, frame_geometry, boxes, nums, call):
+        """This step's per-frame augmentation parameters (augment.draw at `call`) and the labels under them (host tensors of
+        max_num_bbox rows: no device read, no synchronisation)."""
+        Bn, rank = int(boxes.shape[0]), this_rank()
+        params = [AUG.draw(self.augment, self.augment["seed"], rank, call, b) for b in range(Bn)]
         src, cnt = boxes.detach().cpu().numpy(), [int(v) for v in torch.as_tensor(nums).reshape(-1)]
         moved = [AUG.transform_boxes(src[b], cnt[b], params[b], frame_geometry.config) for b in range(Bn)]
         new_boxes = torch.from_numpy(np.stack([m[0] for m in moved], 0)).to(boxes.dtype)
@@ -1192,9 +946,8 @@ def evaluate(training, tester, dataset, loader, max_batches=None):
             x_lidar, geom = training.geometry_async(dataset.geometry, batch["points"], crts=batch.get("crt"), wait_event=batch.event)
             extra = {}
             if getattr(tester, "_kitti", None) is not None and tester._kitti() is not None:      # eval_protocol: kitti
-                crts = batch.get("crt")                                    # the matrices geometry_async projected this batch with
-                extra = dict(levels=batch.get("bbox_level"), dontcare=batch.get("dontcare"),
-                             crt=[dataset.geometry.crt if (crts is None or crts[b] is None) else crts[b] for b in range(len(batch["points"]))])
+                extra = dict(levels=batch.get("bbox_level"), dontcare=batch.get("dontcare"),    # crt: what geometry_async projected this batch with
+                             crt=own_crts(dataset.geometry.crt, batch.get("crt"), len(batch["points"])))
             value, _ = tester.get_eval_value_onestep(x_lidar, batch["image"], batch["bboxes"], batch["num_bboxes"], geom=geom, **extra)
             cum += value
             if max_batches is not None and n >= max_batches:

@@ -14,6 +14,7 @@ nearer labelled object of the frame is not pasted at all.  All numpy, no state.
 """
 import numpy as np
 
+from . import cfgcheck as C
 from . import paste
 
 MAX_OCCLUDERS = 16         # occluders per frame: one per patch record (paste.MAX_RECORDS)
@@ -29,17 +30,8 @@ def parse_config(config):
     blk = config.get("camera_mask", None)
     if blk is None:
         return None
-    if not isinstance(blk, dict):
-        raise ValueError("camera_mask must be a mapping (got %r)" % (blk,))
-    unknown = sorted(set(blk) - set(KEYS))
-    if unknown:
-        raise ValueError("camera_mask: unknown keys %s (known: %s)" % (unknown, list(KEYS)))
-    out = {}
-    for key in KEYS:
-        v = blk.get(key, False)
-        if not isinstance(v, bool):
-            raise ValueError("camera_mask.%s must be true or false (got %r)" % (key, v))
-        out[key] = v
+    C.block("camera_mask", blk, KEYS)
+    out = {key: C.flag("camera_mask." + key, blk.get(key, False)) for key in KEYS}
     return out if (out["fov_crop"] or out["paste_occlusion"]) else None
 
 
