@@ -1,7 +1,9 @@
 // ev_geom.h -- the fp64 rotated-rectangle geometry shared by the evaluation post-processing (evalpost.hip) and the anchor
 // assignment of `loss_sampling: anchor` (loss.hip): rectangle corners, Sutherland-Hodgman clip, shoelace area, bird's-eye IoU.
 // evalgeom.py / evalrank.bev_iou are the host statements; tests/test_gpu_eval.py and tests/test_gpu_eval_ranked.py pin these functions
-// through the evaluation kernels.  ev_clip keeps two 12-vertex polygons per lane in scratch.
+// through the evaluation kernels, and tests/test_gpu_iou_exact.py pins them to an exact rational clip where an edge of one rectangle
+// lies on the line of an edge of the other up to rounding (tests/test_iou_exact_host.py does the same for the host statement, and shows
+// that no pass holds more than 8 vertices there).  ev_clip keeps two 12-vertex polygons per lane in scratch.
 #pragma once
 #include "dcf_common.h"
 
@@ -36,8 +38,7 @@ __device__ int ev_clip(const double (*subject)[2], const double (*clip)[2], doub
             const double sp = ex * (cur[i][1] - ay) - ey * (cur[i][0] - ax);
             const double sq = ex * (cur[q][1] - ay) - ey * (cur[q][0] - ax);
             if ((sp > 0) != (sq > 0)) {
-                const double den = ex * (cur[i][1] - cur[q][1]) - ey * (cur[i][0] - cur[q][0]);
-                const double t = (ex * (ay - cur[q][1]) - ey * (ax - cur[q][0])) / den;
+                const double t = sq / (sq - sp);         // opposite signs: never 0/0, always in [0, 1], also when both are rounding noise
                 nxt[m][0] = cur[q][0] + t * (cur[i][0] - cur[q][0]);
                 nxt[m][1] = cur[q][1] + t * (cur[i][1] - cur[q][1]);
                 ++m;

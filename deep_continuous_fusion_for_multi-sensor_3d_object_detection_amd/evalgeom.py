@@ -10,7 +10,9 @@ which oracle/gen_golden.py produces by running the imported reference (its IOU.p
   * bev_rect / rects_overlap = the rectangle and the separating-axis test of NMS_SAT (test.py:142-175): footprints in
                        (x, y) with size[0] along the heading; touching rectangles count as overlapping
 Known difference: two IDENTICAL boxes are a degenerate input of the reference's clipping (all vertices on the clip edges
-of a strict half-plane test; it returns values between -11 and 3.5 for them); here the IoU of a box with itself is 1.
+of a strict half-plane test; it returns values between -11 and 3.5 for them); here the IoU of a box with itself is 1, and two
+boxes of which one edge lies on the line of an edge of the other up to rounding (concentric boxes of one heading, copies one ulp
+apart) get their IoU to 1e-9 of the exact rational value: tests/test_iou_exact_host.py, and tests/test_gpu_iou_exact.py for the device.
 """
 import math
 
@@ -35,8 +37,13 @@ def _shoelace(poly):
     return 0.5 * abs(float(np.dot(x, np.roll(y, 1)) - np.dot(y, np.roll(x, 1))))
 
 
-def _clip_convex(subject, clip):
-    """Intersection polygon of `subject` with the convex, counter-clockwise polygon `clip` (half-plane by half-plane)."""
+def _clip_convex(subject, clip, counts=None):
+    """Intersection polygon of `subject` with the convex, counter-clockwise polygon `clip` (half-plane by half-plane).
+
+    A crossing is placed by the two side values, t = sq / (sq - sp): they have opposite signs there (at most one is 0), so the
+    denominator is never 0 and t lies in [0, 1] -- also when an edge of `subject` lies on the line a->b up to rounding and both side
+    values are noise, where a parameter taken from two fresh cross products is noise over noise (0/0, or far outside [0, 1]).
+    counts: a list that receives the vertex count after each pass (the device keeps 12 per polygon, csrc/ev_geom.h)."""
     out = [tuple(p) for p in subject]
     a = tuple(clip[-1])
     for b in clip:
@@ -49,13 +56,14 @@ def _clip_convex(subject, clip):
         for i, p in enumerate(out):
             q, sq, sp = out[i - 1], side[i - 1], side[i]
             if (sp > 0) != (sq > 0):                                          # the edge q->p crosses the line a->b
-                den = ex * (p[1] - q[1]) - ey * (p[0] - q[0])
-                t = (ex * (a[1] - q[1]) - ey * (a[0] - q[0])) / den
+                t = sq / (sq - sp)
                 nxt.append((q[0] + t * (p[0] - q[0]), q[1] + t * (p[1] - q[1])))
             if sp > 0:
                 nxt.append(p)
         out = nxt
         a = b
+        if counts is not None:
+            counts.append(len(out))
     return out
 
 
