@@ -294,6 +294,13 @@ struct Corner8 {
     float w[8];
 };
 
+// The one rule of every voxeliser mode: a corner whose FLAT index lies outside [0, nvox) contributes nothing and is never used
+// as an address, of the grid or of the owner workspace.  (A corner that runs one past the end of a row stays inside: it is the
+// first voxel of the next row, see k_voxel_cell_gather.)  Limits without a cell of margin reach such corners: on a 32x64x32 grid
+// with aff 4,0,4,16,10,24 the last floats below z = 0.6f give fz == 30.0, and with xl == 63 the corners (zl+1, xl+1, .) lie
+// past the last voxel.  The lower corner -- the cell -- is kept inside by the entries' host-side check (voxel_cells_inside).
+__device__ __forceinline__ bool vox_inside(int v, int nvox) { return (unsigned)v < (unsigned)nvox; }
+
 // index affine = fl(fl(p*scale)+offset)  (the sgemm chain on the sparse 4x3 matrix)
 __device__ __forceinline__ void corners(float x, float y, float z, const Aff6 &a, int L, int W, Corner8 &o)
 {
@@ -327,14 +334,14 @@ __global__ void __launch_bounds__(256) k_voxel_compat_round(const float *pts, in
         const int c = round - 1;
         int *ow = owner + (size_t)(c & 1) * nvox;
         const int v = c8.vox[c];
-        if (ow[v] == i + 1) {  // this point is the last writer of pass c
+        if (vox_inside(v, nvox) && ow[v] == i + 1) {  // this point is the last writer of pass c
             grid[v] = __fadd_rn(grid[v], c8.w[c]);
             ow[v] = 0;
         }
     }
     if (round <= 7) {
         int *ow = owner + (size_t)(round & 1) * nvox;
-        atomicMax(&ow[c8.vox[round]], i + 1);
+        if (vox_inside(c8.vox[round], nvox)) atomicMax(&ow[c8.vox[round]], i + 1);
     }
 }
 
@@ -374,6 +381,7 @@ __global__ void __launch_bounds__(256) k_voxel_cell_claim(VoxBatch vb, Lim6 lim,
               zl = (int)__fadd_rn(__fmul_rn(z, aff.v[4]), aff.v[5]);
     int *last = owners + (size_t)b * 2 * nvox;
     const int cell = (zl * L + xl) * W + yl;
+    if (!vox_inside(cell, nvox)) return;
     if (release) last[cell] = 0;
     else atomicMax(&last[cell], i + 1);
 }
@@ -393,7 +401,8 @@ __global__ void __launch_bounds__(256) k_voxel_cell_gather(VoxBatch vb, Lim6 lim
     const int xl = (int)__fadd_rn(__fmul_rn(x, aff.v[0]), aff.v[1]), yl = (int)__fadd_rn(__fmul_rn(y, aff.v[2]), aff.v[3]),
               zl = (int)__fadd_rn(__fmul_rn(z, aff.v[4]), aff.v[5]);
     const int *last = owners + (size_t)b * 2 * nvox;
-    if (last[(zl * L + xl) * W + yl] != i + 1) return;              // not the last point of its cell
+    const int cell = (zl * L + xl) * W + yl;
+    if (!vox_inside(cell, nvox) || last[cell] != i + 1) return;     // not the last point of its cell
     TO *grid = grids + (size_t)b * nvox;
     // contrib[k][c]: what pass c adds to this cell's corner k.  The contributor of (k, c) is the last point of the cell at
     // offset e_k - e_c (e = the corner's (z, x, y) bits), so the 27 neighbouring cells are visited once each -- one claim
@@ -406,8 +415,8 @@ __global__ void __launch_bounds__(256) k_voxel_cell_gather(VoxBatch vb, Lim6 lim
         for (int c = 0; c < 8; ++c) contrib[k][c] = 0.f;
     // (everything in FLAT voxel indices, like the reference's index arithmetic on the flattened grid: a corner index one
     // past the end of a row is the first voxel of the next row -- only reachable with limits that leave less than one
-    // cell of margin, but the nine-round formulation and the CPU restatement behave that way)
-    const int cell = (zl * L + xl) * W + yl;
+    // cell of margin, but the nine-round formulation and the CPU restatement behave that way; an index outside [0, nvox) is
+    // dropped in every formulation: vox_inside)
 #pragma unroll
     for (int oz = -1; oz <= 1; ++oz)
 #pragma unroll
@@ -415,7 +424,7 @@ __global__ void __launch_bounds__(256) k_voxel_cell_gather(VoxBatch vb, Lim6 lim
 #pragma unroll
             for (int oy = -1; oy <= 1; ++oy) {
                 const int nc = cell + (oz * L + ox) * W + oy;
-                if (nc < 0 || nc >= nvox) continue;
+                if (!vox_inside(nc, nvox)) continue;
                 const int j1 = last[nc];
                 if (j1 <= 0) continue;
                 const float *q = pts + 3 * (size_t)(j1 - 1);
@@ -437,7 +446,7 @@ __global__ void __launch_bounds__(256) k_voxel_cell_gather(VoxBatch vb, Lim6 lim
 #pragma unroll
         for (int c = 0; c < 8; ++c) sum = __fadd_rn(sum, contrib[k][c]);                       // pass order
         const int v = cell + ((k & 1) * L + ((k >> 1) & 1)) * W + ((k >> 2) & 1);
-        if (v >= nvox) continue;
+        if (!vox_inside(v, nvox)) continue;
         if (NHWC) {
             const int vz = v / (L * W), r = v - vz * (L * W);
             DT<TO>::st(grid + (size_t)r * Cz + vz, sum);                                       // r = vx*W + vy
@@ -447,7 +456,7 @@ __global__ void __launch_bounds__(256) k_voxel_cell_gather(VoxBatch vb, Lim6 lim
     }
 }
 
-__global__ void __launch_bounds__(256) k_voxel_accum(const float *pts, int n, Lim6 lim, Aff6 aff, int L, int W, float *grid)
+__global__ void __launch_bounds__(256) k_voxel_accum(const float *pts, int n, Lim6 lim, Aff6 aff, int L, int W, int nvox, float *grid)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -456,12 +465,13 @@ __global__ void __launch_bounds__(256) k_voxel_accum(const float *pts, int n, Li
     Corner8 c8;
     corners(x, y, z, aff, L, W, c8);
 #pragma unroll
-    for (int c = 0; c < 8; ++c) atomicAdd(&grid[c8.vox[c]], c8.w[c]);
+    for (int c = 0; c < 8; ++c)
+        if (vox_inside(c8.vox[c], nvox)) atomicAdd(&grid[c8.vox[c]], c8.w[c]);
 }
 
 // interpolate=False (data_import_carla.py:231-234): the voxel holding the point (trunc'd ids = lower corner) is set to 1;
 // every writer stores the same value, so the result does not depend on the order
-__global__ void __launch_bounds__(256) k_voxel_occupancy(const float *pts, int n, Lim6 lim, Aff6 aff, int L, int W, float *grid)
+__global__ void __launch_bounds__(256) k_voxel_occupancy(const float *pts, int n, Lim6 lim, Aff6 aff, int L, int W, int nvox, float *grid)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -469,7 +479,7 @@ __global__ void __launch_bounds__(256) k_voxel_occupancy(const float *pts, int n
     if (!in_range(x, y, z, lim)) return;
     Corner8 c8;
     corners(x, y, z, aff, L, W, c8);
-    grid[c8.vox[0]] = 1.0f;
+    if (vox_inside(c8.vox[0], nvox)) grid[c8.vox[0]] = 1.0f;
 }
 
 // ------------------------------------------------------------------------------
@@ -1560,12 +1570,48 @@ extern "C" int dcf_augment_points_batch(const float *const *pts, const int *n, i
 
 extern "C" size_t dcf_voxelize_workspace_bytes(int Cz, int L, int W) { return sizeof(int) * 2 * (size_t)Cz * L * W; }
 
+// Host-side check of the voxeliser entries: can the LOWER corner of an accepted point -- its cell, flat index
+// (zl*L + xl)*W + yl -- leave [0, nvox)?  The kernels' own chain fl(fl(p*s)+o) is monotone in p, and so is the truncation, so
+// per axis the extreme cell indices are those of the first float above the lower limit and the last float below the upper one
+// (both ends are evaluated: a negative scale swaps them).  The flat index is monotone in each of the three, so its extremes are
+// those of the extremes.  Upper corners are not judged here: limits without a cell of margin are legal, their out-of-grid
+// corners are dropped by the kernels (vox_inside).  An axis whose open interval holds no float accepts no point at all.
+static bool voxel_cells_inside(const float *lim, const float *aff, int Cz, int L, int W, int64_t *lo_flat, int64_t *hi_flat)
+{
+    int64_t lo[3], hi[3];                   // x, y, z
+    for (int ax = 0; ax < 3; ++ax) {
+        const float p0 = nextafterf(lim[2 * ax], INFINITY), p1 = nextafterf(lim[2 * ax + 1], -INFINITY);
+        if (!(p0 <= p1)) { *lo_flat = *hi_flat = 0; return true; }
+        const float t0 = p0 * aff[2 * ax], t1 = p1 * aff[2 * ax];
+        const float f0 = t0 + aff[2 * ax + 1], f1 = t1 + aff[2 * ax + 1];
+        if (!(fabsf(f0) < 1073741824.0f && fabsf(f1) < 1073741824.0f)) return false;        // (int) of it is not defined
+        const int64_t c0 = (int64_t)(int)f0, c1 = (int64_t)(int)f1;
+        lo[ax] = c0 < c1 ? c0 : c1;
+        hi[ax] = c0 < c1 ? c1 : c0;
+    }
+    *lo_flat = (lo[2] * L + lo[0]) * W + lo[1];
+    *hi_flat = (hi[2] * L + hi[0]) * W + hi[1];
+    return *lo_flat >= 0 && *hi_flat < (int64_t)Cz * L * W;
+}
+
+static int voxel_guard(const char *who, const float *lim, const float *aff, int Cz, int L, int W)
+{
+    for (int k = 0; k < 6; ++k)
+        DCF_REQUIRE(fabsf(lim[k]) <= 3.402823466e38f && fabsf(aff[k]) <= 3.402823466e38f, "%s: lim and aff must be finite", who);   // (false for a NaN)
+    int64_t lo = 0, hi = 0;
+    DCF_REQUIRE(voxel_cells_inside(lim, aff, Cz, L, W, &lo, &hi),
+                "%s: a point inside the limits can fall into a cell outside the grid (flat cell index %lld .. %lld of %lld voxels)", who,
+                (long long)lo, (long long)hi, (long long)Cz * L * W);
+    return DCF_OK;
+}
+
 
 extern "C" int dcf_voxelize(const float *pts, int n, const float *lim, const float *aff, int Cz, int L, int W,
                             int mode, float *grid, void *owner_ws, dcf_stream_t stream)
 {
     DCF_REQUIRE(n >= 0 && lim && aff && grid && Cz > 0 && L > 0 && W > 0, "dcf_voxelize: bad arguments");
     DCF_REQUIRE((int64_t)Cz * L * W < (1ll << 31), "dcf_voxelize: grid too large for int32 voxel ids");
+    if (int rc = voxel_guard("dcf_voxelize", lim, aff, Cz, L, W)) return rc;        // refused before anything is launched
     hipStream_t s = S(stream);
     const int nvox = Cz * L * W;
     DCF_HIP(hipMemsetAsync(grid, 0, sizeof(float) * (size_t)nvox, s));
@@ -1588,9 +1634,9 @@ extern "C" int dcf_voxelize(const float *pts, int n, const float *lim, const flo
             DCF_LAUNCH("voxel_compat_round", s, hipLaunchKernelGGL(k_voxel_compat_round, dim3(nb), dim3(256), 0, s, pts, n, l, a, L, W, nvox, r,
                                                                    grid, (int *)owner_ws));
     } else if (mode == DCF_VOXEL_ACCUM) {
-        DCF_LAUNCH("voxel_accum", s, hipLaunchKernelGGL(k_voxel_accum, dim3(nb), dim3(256), 0, s, pts, n, l, a, L, W, grid));
+        DCF_LAUNCH("voxel_accum", s, hipLaunchKernelGGL(k_voxel_accum, dim3(nb), dim3(256), 0, s, pts, n, l, a, L, W, nvox, grid));
     } else if (mode == DCF_VOXEL_OCCUPANCY) {
-        DCF_LAUNCH("voxel_occupancy", s, hipLaunchKernelGGL(k_voxel_occupancy, dim3(nb), dim3(256), 0, s, pts, n, l, a, L, W, grid));
+        DCF_LAUNCH("voxel_occupancy", s, hipLaunchKernelGGL(k_voxel_occupancy, dim3(nb), dim3(256), 0, s, pts, n, l, a, L, W, nvox, grid));
     } else {
         dcf_set_error("dcf_voxelize: unknown mode %d", mode);
         return DCF_EINVAL;
@@ -1604,6 +1650,7 @@ static int voxelize_batch_impl(const char *who, int dtype, bool nhwc, const floa
     DCF_REQUIRE(pts && n && lim && aff && grids && owner_ws && Cz > 0 && L > 0 && W > 0, "%s: bad arguments", who);
     DCF_REQUIRE(B >= 1 && B <= DCF_MAX_VOXEL_BATCH, "%s: 1..%d frames per call", who, DCF_MAX_VOXEL_BATCH);
     DCF_REQUIRE((int64_t)Cz * L * W < (1ll << 31), "%s: grid too large for int32 voxel ids", who);
+    if (int rc = voxel_guard(who, lim, aff, Cz, L, W)) return rc;                   // refused before anything is launched
     const int nvox = Cz * L * W;
     const size_t es = dtype == DCF_F32 ? 4 : 2;
     DCF_HIP(hipMemsetAsync(grids, 0, es * (size_t)nvox * B, s));

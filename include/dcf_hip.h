@@ -72,7 +72,16 @@ int dcf_range_filter(const float *pts, int n, const float *lim, float *out_pts, 
  * aff HOST float[6] = {sx,ox,sy,oy,sz,oz}.  grid [Cz][L][W] fp32 is fully written.
  * mode COMPAT: bit-exact "last writer wins per corner pass" (SURVEY.md F3);
  *      ACCUM : atomic trilinear splat.
- * owner_ws: int32[2][Cz*L*W], must be ZERO on entry and is returned ZERO (COMPAT only). */
+ *      COMPAT_ROUNDS: the same grid by the literal nine rounds;  OCCUPANCY: the point's cell is set to 1.
+ * owner_ws: int32[2][Cz*L*W], must be ZERO on entry and is returned ZERO (COMPAT, COMPAT_ROUNDS only).
+ * Corners and the grid's end.  Indices are FLAT, v = (z*L + x)*W + y, as in the reference: a corner one past the end of a row
+ * is the first voxel of the next row and is kept.  In every mode, and in the batch entries below, a corner whose flat index
+ * lies outside [0, Cz*L*W) contributes nothing and is never used as an address -- of the grid or of owner_ws.  Limits that
+ * leave less than a cell of margin reach such corners (32x64x32, aff 4,0,4,16,10,24: the last two floats below z = 0.6f have
+ * fz == 30.0, and with xl == 63 the corners (zl+1, xl+1, .) lie past the last voxel); that is legal.
+ * Refused with DCF_EINVAL, nothing launched, nothing written: a non-finite lim or aff; limits under which the LOWER corner
+ * (the point's own cell) can leave [0, Cz*L*W) -- judged with the kernels' chain fl(fl(p*s)+o) at the first float above
+ * each lower limit and the last float below each upper limit (both ends per axis, so a negative scale is handled). */
 size_t dcf_voxelize_workspace_bytes(int Cz, int L, int W);
 int dcf_voxelize(const float *pts, int n, const float *lim, const float *aff, int Cz, int L, int W,
                  int mode, float *grid, void *owner_ws, dcf_stream_t stream);
@@ -163,7 +172,11 @@ int dcf_paste_patches_batch(const uint8_t *img, int B, int H, int W, const int *
 
 /* BEV K-nearest-neighbour (reference: model.py:199-203 TODO; spec SURVEY.md App. D).
  * xyz [n_max][3], first *count_dev rows valid.  idx_out int32 [K][h][w], -1 padding.
- * rmax2 < 0 = unbounded.  K <= 8.  ws: dcf_knn_workspace_bytes(n_max,h,w). */
+ * rmax2 < 0 = unbounded.  K <= 8.  ws: dcf_knn_workspace_bytes(n_max,h,w).
+ * Order: ascending (d2, index), d2 = fl(fl(dx dx) + fl(dy dy)) to the pixel centre; d2 == rmax2 is kept.  A point outside
+ * the site is sorted into the nearest border cell and takes part with its true distance.  The valid rows are FINITE by
+ * construction -- they are what dcf_project_filter kept, and its range test rejects NaN and infinite coordinates; the
+ * result for a non-finite valid row is not defined (rows past *count_dev may hold anything). */
 size_t dcf_knn_workspace_bytes(int n_max, int h, int w);
 int dcf_knn_bev(const float *xyz, const int32_t *count_dev, int n_max, int K, int h, int w, int stride,
                 float xs, float xo, float ys, float yo, float rmax2, int32_t *idx_out, void *ws,

@@ -95,17 +95,31 @@ void dcf_oracle_voxelize(const float *pts, int n, const float *aff,
             wgt[(size_t)i * 8 + c] = w[c];
         }
     }
+    /* One rule in every mode: a corner whose flat index lies outside [0, nvox) contributes nothing and is never used as an
+     * address.  (Limits without a cell of margin reach such corners; a corner one past the end of a ROW stays inside the
+     * flattened grid -- it is the first voxel of the next row -- and is kept, as the reference's flat index arithmetic keeps it.) */
+    const int64_t nvox = (int64_t)Cz * L * W;
+#define VOX_IN(v) ((v) >= 0 && (v) < nvox)
     if (mode == 0) {
         for (int c = 0; c < 8; ++c) {
-            for (int i = 0; i < n; ++i) tmp[i] = grid[vox[(size_t)i * 8 + c]] + wgt[(size_t)i * 8 + c];
-            for (int i = 0; i < n; ++i) grid[vox[(size_t)i * 8 + c]] = tmp[i];
+            for (int i = 0; i < n; ++i) {
+                int64_t v = vox[(size_t)i * 8 + c];
+                if (VOX_IN(v)) tmp[i] = grid[v] + wgt[(size_t)i * 8 + c];
+            }
+            for (int i = 0; i < n; ++i) {
+                int64_t v = vox[(size_t)i * 8 + c];
+                if (VOX_IN(v)) grid[v] = tmp[i];
+            }
         }
     } else if (mode == 2) {
-        for (int i = 0; i < n; ++i) grid[vox[(size_t)i * 8]] = 1.0f;
+        for (int i = 0; i < n; ++i)
+            if (VOX_IN(vox[(size_t)i * 8])) grid[vox[(size_t)i * 8]] = 1.0f;
     } else {
         for (int i = 0; i < n; ++i)
-            for (int c = 0; c < 8; ++c) grid[vox[(size_t)i * 8 + c]] += wgt[(size_t)i * 8 + c];
+            for (int c = 0; c < 8; ++c)
+                if (VOX_IN(vox[(size_t)i * 8 + c])) grid[vox[(size_t)i * 8 + c]] += wgt[(size_t)i * 8 + c];
     }
+#undef VOX_IN
     free(vox); free(wgt); free(tmp);
 }
 
