@@ -163,6 +163,9 @@ SIGNATURES = {
     "dcf_loss_anchor_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dcf_loss_anchor_fwd_bwd": (c_int, [P, c_i64, P, c_i64, P, P, c_int, c_int, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_int,
                                         P, P, c_i64, P, c_i64, P, P, P]),
+    # iou_loss_gain: the rotated-IoU regression term on the same targets (csrc/loss_iou.hip)
+    "dcf_loss_anchor_iou_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dcf_loss_anchor_iou_fwd_bwd": (c_int, [P, c_i64, P, P, c_int, c_int, P, P, c_int, c_int, c_int, c_int, c_float, c_int, P, P, c_i64, P, P, P, P]),
     "dcf_adam_step": (c_int, [P, P, P, P, c_i64, c_float, c_float, c_float, c_float, c_int, c_float, P]),
     "dcf_grad_stats": (c_int, [P, c_i64, P, P]),
     "dcf_amp_update": (c_int, [P, c_float, c_int, ctypes.c_double, ctypes.c_double, c_int, c_float, c_float, c_float, c_float, P]),

@@ -26,6 +26,10 @@ bird's-eye IoU with the labels (positive from assign_pos_iou, negative below ass
 label forced positive; assign.py is the host statement, csrc/loss.hip k_assign_* the device's), the focal term runs over the anchors
 that are not ignored and the regression over the positive ones (anchor_terms() below; k_loss_anchor).  No windows, nothing drawn.
 
+`iou_loss_gain` > 0 (anchor mode only) adds gain * mean over the positive anchors of (1 - rotated IoU of the decoded box with its label)
+per sample: anchor_iou_terms() / iou_value_grad() below are the host statements, csrc/loss_iou.hip the device's (one lane per positive
+anchor, compacted in index order; no atomics).  LossTotal.last_iou then holds (mean IoU of the positives, N_b) per sample.
+
 Reference quirks are kept behind `loss_reduction: last` (default): cross-entropy on already
 soft-maxed scores (loss.py:17-20,139), 129 negatives (:125), only the last sample of the
 batch contributes (:71).  'sum' / 'mean' accumulate over the batch instead.
@@ -224,6 +228,163 @@ def anchor_terms(cls_b, reg_b, anchors, boxes, target, alpha, gamma, eps):
     return cls_value * inv_n, reg_value * (inv_n / 7.0), n_pos, gcls, greg
 
 
+IOU_KIND = {"3d": 0, "bev": 1}                     # the kernel's kind codes (csrc/loss_iou.hip)
+
+
+def parse_iou_loss_config(config):
+    """(iou_loss_gain, iou_loss_kind), validated: the gain a finite number >= 0 (absent or 0: the term is off), the kind '3d' or 'bev';
+    a gain > 0 needs `loss_sampling: anchor` (the term runs over that mode's per-anchor targets; there is no fallback)."""
+    from . import cfgcheck
+    gain = cfgcheck.number("iou_loss_gain", config.get("iou_loss_gain", 0.0), nonneg=True)
+    kind = config.get("iou_loss_kind", "3d")
+    if not isinstance(kind, str) or kind not in IOU_KIND:
+        raise ValueError("iou_loss_kind must be '3d' or 'bev' (got %r)" % (kind,))
+    if gain > 0 and config.get("loss_sampling", "compat") != "anchor":
+        raise ValueError("iou_loss_gain > 0 needs loss_sampling: anchor (got loss_sampling: %r)" % (config.get("loss_sampling", "compat"),))
+    return gain, kind
+
+
+def decode_offsets(r, an):
+    """The head's box decode (csrc/elementwise.hip, k_head_fwd) in float64, without the yaw wrap: r [7, m] offsets, an [7, m] anchors ->
+    (boxes [7, m] = x, y, z, l, w, h, yaw; chain [7, m] = d box_c / d r_c = diag, diag, a5, l, w, h, 1)."""
+    r, an = np.asarray(r, dtype=np.float64), np.asarray(an, dtype=np.float64)
+    diag = np.sqrt(an[3] ** 2 + an[4] ** 2)
+    with np.errstate(over="ignore", invalid="ignore"):
+        l, w, h = np.exp(r[3]) * an[3], np.exp(r[4]) * an[4], np.exp(r[5]) * an[5]
+        box = np.stack((r[0] * diag + an[0], r[1] * diag + an[1], r[2] * an[5] + an[2], l, w, h, r[6] + an[6]))
+    return box, np.stack((diag, diag, an[5], l, w, h, np.ones_like(diag)))
+
+
+def _rects(x, y, l, w, yaw):
+    """evalgeom.bev_rect for arrays: corners [m, 4, 2], counter-clockwise, corner k = (sl, sw)[k] half-sizes along / across the heading."""
+    c, s = np.cos(yaw), np.sin(yaw)
+    hl, hw = l / 2, w / 2
+    out = np.empty(x.shape + (4, 2))
+    for k, (sl, sw) in enumerate(((-1, -1), (1, -1), (1, 1), (-1, 1))):
+        out[:, k, 0] = x + sl * hl * c - sw * hw * s
+        out[:, k, 1] = y + sl * hl * s + sw * hw * c
+    return out
+
+
+def _edges_inside(P, Q, closed):
+    """Every edge k of the rectangles P [m, 4, 2] (corner k to k + 1) clipped parametrically against the four half-planes of Q: (t0, t1)
+    [m, 4] each, the piece inside is A + t (B - A) for t in [t0, t1], empty when t1 <= t0.  Strictly left of an edge of Q is inside, the
+    side values and the crossing parameter sa / (sa - sb) are those of evalgeom._clip_convex; with `closed` an edge that lies ON a line
+    of Q (both side values exactly 0) stays, so that of two coincident edges one is kept (P's) and one dropped (Q's).  A NaN compares
+    false everywhere: the edge is empty."""
+    A, Bv = P, np.roll(P, -1, axis=1)
+    t0, t1 = np.zeros(P.shape[:2]), np.ones(P.shape[:2])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for j in range(4):
+            a, b = Q[:, j, None, :], Q[:, (j + 1) % 4, None, :]
+            ex, ey = b[..., 0] - a[..., 0], b[..., 1] - a[..., 1]
+            sa = ex * (A[..., 1] - a[..., 1]) - ey * (A[..., 0] - a[..., 0])
+            sb = ex * (Bv[..., 1] - a[..., 1]) - ey * (Bv[..., 0] - a[..., 0])
+            ina, inb = sa > 0, sb > 0
+            t = sa / (sa - sb)
+            t1 = np.where(ina & ~inb, np.minimum(t1, t), t1)
+            t0 = np.where(inb & ~ina, np.maximum(t0, t), t0)
+            out = ~ina & ~inb
+            if closed:
+                out &= ~((sa == 0) & (sb == 0))
+            t1 = np.where(out, -1.0, t1)
+    return t0, t1
+
+
+def iou_value_grad(p, q, kind="3d"):
+    """The edge-clip form of the rotated IoU of boxes p [m, 7] against q [m, 7] (x, y, z, l, w, h, yaw; z at mid-height) and its derivative
+    by p, in float64: (iou [m], d iou / d p [m, 7]).  This is the arithmetic of csrc/loss_iou.hip; its value agrees with
+    evalkitti.iou_pair (the polygon clip) to rounding wherever no edge of one rectangle lies on the line of an edge of the other.
+
+    Coordinates are taken relative to q's centre.  Each of p's edges is clipped in q and each of q's edges in p (_edges_inside); the
+    pieces are the boundary of the intersection, so I = half the sum of cross(a, b) over the pieces = half the sum of (t1 - t0) cross(A, B)
+    over the edges.  p's edge k has the outward normal n_k = (s, -c), (c, s), (-s, c), (-c, -s) (c, s = cos, sin of p's yaw), length
+    len_k = (t1 - t0) times l (k = 0, 2: the sides) or w (k = 1, 3: front and rear) and midpoint m_k:
+        dI/dx = sum n_kx len_k, dI/dy = sum n_ky len_k, dI/dyaw = sum len_k (n_ky (m_kx - x) - n_kx (m_ky - y)),
+        dI/dl = (len_1 + len_3) / 2, dI/dw = (len_0 + len_2) / 2.
+    zo = max(0, min(tops) - max(bottoms)); d zo/dz = [p's top is the lower] - [p's bottom is the higher], d zo/dh = half their sum, both 0
+    when zo = 0.  I3 = I zo, U = l w h + V_q - I3, d iou = (dI3 U - I3 dU) / U^2 with dU = d(l w h) - dI3; 'bev': zo = 1 and areas for
+    volumes.  A disjoint pair has iou 0 and seven exact zeros; a row with a non-finite p or q has NaN everywhere."""
+    if kind not in IOU_KIND:
+        raise ValueError("kind must be '3d' or 'bev' (got %r)" % (kind,))
+    p, q = np.asarray(p, dtype=np.float64).reshape(-1, 7), np.asarray(q, dtype=np.float64).reshape(-1, 7)
+    m = p.shape[0]
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        x, y = p[:, 0] - q[:, 0], p[:, 1] - q[:, 1]
+        l, w, h, yaw = p[:, 3], p[:, 4], p[:, 5], p[:, 6]
+        c, s = np.cos(yaw), np.sin(yaw)
+        P, Q = _rects(x, y, l, w, yaw), _rects(np.zeros(m), np.zeros(m), q[:, 3], q[:, 4], q[:, 6])
+        cross = lambda R: R[:, :, 0] * np.roll(R, -1, axis=1)[:, :, 1] - R[:, :, 1] * np.roll(R, -1, axis=1)[:, :, 0]
+        pt0, pt1 = _edges_inside(P, Q, closed=True)
+        qt0, qt1 = _edges_inside(Q, P, closed=False)
+        pd, qd = np.maximum(0.0, pt1 - pt0), np.maximum(0.0, qt1 - qt0)
+        I = 0.5 * ((pd * cross(P)).sum(1) + (qd * cross(Q)).sum(1))
+        length = pd * np.stack((l, w, l, w), 1)
+        tm = 0.5 * (pt0 + pt1)[..., None]
+        mid = P + tm * (np.roll(P, -1, axis=1) - P)                       # [m, 4, 2]
+        nx, ny = np.stack((s, c, -s, -c), 1), np.stack((-c, s, c, -s), 1)
+        dI = np.zeros((m, 7))
+        dI[:, 0], dI[:, 1] = (nx * length).sum(1), (ny * length).sum(1)
+        dI[:, 3], dI[:, 4] = 0.5 * (length[:, 1] + length[:, 3]), 0.5 * (length[:, 0] + length[:, 2])
+        dI[:, 6] = (length * (ny * (mid[:, :, 0] - x[:, None]) - nx * (mid[:, :, 1] - y[:, None]))).sum(1)
+        dS = np.zeros((m, 7))                                             # d (l w) or d (l w h)
+        if kind == "bev":
+            zo, dzo = np.ones(m), np.zeros((m, 7))
+            size, vq = l * w, q[:, 3] * q[:, 4]
+            dS[:, 3], dS[:, 4] = w, l
+        else:
+            top_p, bot_p, top_q, bot_q = p[:, 2] + h / 2, p[:, 2] - h / 2, q[:, 2] + q[:, 5] / 2, q[:, 2] - q[:, 5] / 2
+            zo = np.maximum(0.0, np.minimum(top_p, top_q) - np.maximum(bot_p, bot_q))
+            lower_top, higher_bot = ((top_p < top_q) & (zo > 0)).astype(np.float64), ((bot_p > bot_q) & (zo > 0)).astype(np.float64)
+            dzo = np.zeros((m, 7))
+            dzo[:, 2], dzo[:, 5] = lower_top - higher_bot, 0.5 * (lower_top + higher_bot)
+            size, vq = l * w * h, q[:, 3] * q[:, 4] * q[:, 5]
+            dS[:, 3], dS[:, 4], dS[:, 5] = w * h, l * h, l * w
+        I3 = I * zo
+        dI3 = dI * zo[:, None] + I[:, None] * dzo
+        U = size + vq - I3
+        iou = I3 / U
+        grad = (dI3 * U[:, None] - I3[:, None] * (dS - dI3)) / (U * U)[:, None]
+    bad = ~(np.isfinite(p).all(1) & np.isfinite(q).all(1))
+    iou[bad], grad[bad] = np.nan, np.nan
+    return iou, grad
+
+
+def anchor_iou_terms(reg_b, anchors, boxes, target, kind="3d"):
+    """The host statement of the IoU regression term (`iou_loss_gain`) for one sample, in float64: reg_b [14, HW],
+    anchors [2, 7, HW], boxes [n, >= 7], target int [2 * HW] as in anchor_terms -> (L = sum over the positive anchors of (1 - IoU(p_j, q_j))
+    / max(1, N), N, the sum of the IoUs, d L / d reg_b [14, HW], the per-anchor IoU [2, HW], 0 where the anchor is not positive).
+    q_j = the label row target(j); p_j = decode_offsets of the anchor's seven offsets.  The VALUE of every IoU is
+    evalkitti.iou_pair(p, q)[1] ('3d') or [0] ('bev') itself; the derivative is iou_value_grad's, chained to the offsets."""
+    from . import evalkitti
+    if kind not in IOU_KIND:
+        raise ValueError("kind must be '3d' or 'bev' (got %r)" % (kind,))
+    r, an = np.asarray(reg_b, dtype=np.float64), np.asarray(anchors, dtype=np.float64)
+    bx = np.asarray(boxes, dtype=np.float64).reshape(-1, np.shape(boxes)[-1] if np.ndim(boxes) > 1 else 7)
+    HW = r.shape[1]
+    t = np.asarray(target, dtype=np.int64).reshape(2, HW).copy()
+    t[(t < -2) | (t >= len(bx))] = -2
+    n_pos = int((t >= 0).sum())
+    inv_n = 1.0 / max(1, n_pos)
+    grad, iou_map = np.zeros((14, HW)), np.zeros((2, HW))
+    value = total = 0.0
+    for a in range(2):
+        cells = np.flatnonzero(t[a] >= 0)
+        if not cells.size:
+            continue
+        p, chain = decode_offsets(r[7 * a:7 * a + 7][:, cells], an[a][:, cells])
+        q = bx[t[a][cells], :7]
+        _, g = iou_value_grad(p.T, q, kind)
+        iou = np.array([evalkitti.iou_pair(p[:, i], q[i])[0 if kind == "bev" else 1] for i in range(cells.size)])
+        iou[~(np.isfinite(p).all(0) & np.isfinite(q).all(1))] = np.nan
+        with np.errstate(invalid="ignore"):
+            value += (1.0 - iou).sum()
+            total += iou.sum()
+            grad[7 * a:7 * a + 7, cells] = -(g.T * chain) * inv_n
+        iou_map[a, cells] = iou
+    return value * inv_n, n_pos, total, grad, iou_map
+
+
 class LossTotal(nn.Module):
     def __init__(self, config):
         super(LossTotal, self).__init__()
@@ -238,6 +399,8 @@ class LossTotal(nn.Module):
         if self.sampling == "anchor":
             from .assign import parse_assign_config
             self.assign_iou = parse_assign_config(config)
+        self.iou_gain, self.iou_kind = parse_iou_loss_config(config)      # the rotated-IoU regression term (anchor only; 0: off)
+        self.last_iou = None               # iou_loss_gain > 0: [B,2] fp32 = (mean IoU of the positive anchors, N_b) of the last call
         self.last_terms = None             # focal: [B,3] fp32 = (cls_b, reg_b without the gain, |P_b|) of the last call, unweighted
                                            # (anchor: the third column is N_b, the positive anchors)
         from .model import parse_deterministic_config
@@ -589,7 +752,9 @@ class LossTotal(nn.Module):
         """loss_sampling: anchor.  CUDA tensors: dcf_assign_anchors_iou on the staged labels, then dcf_loss_anchor_fwd_bwd on its
         targets -- five small launches on one stream, no host wait; workspaces, target and counts are allocated once per map shape.
         CPU tensors: the host statements (assign.anchor_targets, anchor_terms) behind the same autograd function.  Nothing is drawn:
-        calls is not advanced.  With keep_samples, last_samples = (target [B,2,HW], best [B,2,HW] fp64, counts [B,4])."""
+        calls is not advanced.  With keep_samples, last_samples = (target [B,2,HW], best [B,2,HW] fp64, counts [B,4]).
+        With iou_loss_gain > 0, dcf_loss_anchor_iou_fwd_bwd follows in the same closure (its workspaces are allocated with the others,
+        and only then); last_iou = [B,2] (mean IoU of the positives, N_b), and last_samples gains the per-anchor fp64 IoU map."""
         c = self.config
         dev = cls.device
         alpha, gamma, eps = self.focal
@@ -600,31 +765,37 @@ class LossTotal(nn.Module):
         if dev.type != "cuda":
             boxes_host = boxes.detach().float()
             if ws is None or ws[0] != key:
-                ws = self._anchor_ws = (key, torch.zeros((B, 3), dtype=torch.float32))
+                ws = self._anchor_ws = (key, torch.zeros((B, 3), dtype=torch.float32), torch.zeros((B, 2), dtype=torch.float32) if self.iou_gain > 0 else None)
             self.last_terms = terms = ws[1]
+            self.last_iou = iou_terms = ws[2]
 
             def launch(loss, gcls, greg):
-                self._anchor_host(boxes_host, nbox, cls.detach(), reg.detach(), anc, B, H, W, loss, gcls, greg, terms)
+                self._anchor_host(boxes_host, nbox, cls.detach(), reg.detach(), anc, B, H, W, loss, gcls, greg, terms, iou_terms)
             return _FusedLoss.apply(None, cls, reg, launch)
         from . import ops
         boxes, nb = self._stage_labels(boxes, nbox, dev)
         base, cls, reg = self._head_views(cls, reg, H, W)
         if ws is None or ws[0] != key:
             ws = self._anchor_ws = ((key,) + ops.assign_anchors_workspace(B, H, W, boxes.shape[1], dev, best=self.keep_samples)
-                                    + ops.loss_anchor_workspace(B, H, W, dev))
-        _, aws, target, counts, best, lws, terms = ws
-        self.last_terms = terms
+                                    + ops.loss_anchor_workspace(B, H, W, dev)
+                                    + (ops.loss_anchor_iou_workspace(B, H, W, dev, iou_map=self.keep_samples) if self.iou_gain > 0 else (None, None, None)))
+        _, aws, target, counts, best, lws, terms, iws, iou_terms, iou_map = ws
+        self.last_terms, self.last_iou = terms, iou_terms
         if self.keep_samples:
-            self.last_samples = (target, best, counts)
+            self.last_samples = (target, best, counts) + ((iou_map,) if self.iou_gain > 0 else ())
+        iou_gain, iou_kind = self.iou_gain, IOU_KIND[self.iou_kind]
 
         def launch(loss, gcls, greg):
             ops.assign_anchors_iou(anc, boxes, nb, H, W, pos_iou, neg_iou, target, counts, aws, best=best)
             ops.loss_anchor(cls, reg, anc, boxes, target, counts, alpha, gamma, eps, gain, red, loss, gcls, greg, terms, lws)
+            if iou_gain > 0:
+                ops.loss_anchor_iou(reg, anc, boxes, target, counts, iou_kind, iou_gain, red, loss, greg, iou_terms, iws, iou_map=iou_map)
         return _FusedLoss.apply(base, cls, reg, launch)
 
-    def _anchor_host(self, boxes_host, nbox, cls, reg, anc, B, H, W, loss, gcls, greg, terms):
-        """The host statement of the two anchor entries: fills loss [1], the gradient maps and terms [B,3] in float64 arithmetic.  The
-        device assigns every sample; here only those the reduction counts, unless keep_samples asks for all."""
+    def _anchor_host(self, boxes_host, nbox, cls, reg, anc, B, H, W, loss, gcls, greg, terms, iou_terms=None):
+        """The host statement of the anchor entries: fills loss [1], the gradient maps and terms [B,3] in float64 arithmetic.  The
+        device assigns every sample; here only those the reduction counts, unless keep_samples asks for all.  With iou_loss_gain > 0
+        anchor_iou_terms adds the IoU term, fills iou_terms [B,2], and last_samples gains the per-anchor IoU map."""
         from . import assign
         alpha, gamma, eps = self.focal
         pos_iou, neg_iou = self.assign_iou
@@ -636,6 +807,11 @@ class LossTotal(nn.Module):
         counted = [B - 1] if self.reduction == "last" else list(range(B))
         w = 1.0 / B if self.reduction == "mean" else 1.0
         kept = (np.full((B, 2, HW), -1, np.int32), np.zeros((B, 2, HW)), np.zeros((B, 4), np.int32)) if self.keep_samples else None
+        iou_on = self.iou_gain > 0
+        if iou_on:
+            iou_terms.zero_()
+            if kept is not None:
+                kept = kept + (np.zeros((B, 2, HW)),)
         for b in (range(B) if kept is not None else counted):
             nb = max(min(int(nbox[b]), bh.shape[1]), 0)
             target, best, counts = assign.anchor_targets(an, bh[b, :nb], pos_iou, neg_iou)
@@ -645,10 +821,18 @@ class LossTotal(nn.Module):
                 continue
             lc, lr, n_pos, gc, gr = anchor_terms(cls[b].reshape(4, HW).double().numpy(), reg[b].reshape(14, HW).double().numpy(), an,
                                                  bh[b, :nb], target, alpha, gamma, eps)
-            gcls[b] = torch.from_numpy(gc * w).to(gcls.dtype).reshape(4, H, W)
-            greg[b] = torch.from_numpy(gr * (gain * w)).to(greg.dtype).reshape(14, H, W)
-            terms[b] = torch.tensor([lc, lr, n_pos], dtype=torch.float32)
+            gr = gr * (gain * w)
             total += w * (lc + gain * lr)
+            if iou_on:
+                li, _, iou_sum, gi, iou_map = anchor_iou_terms(reg[b].reshape(14, HW).double().numpy(), an, bh[b, :nb], target, self.iou_kind)
+                gr = gr + gi * (self.iou_gain * w)
+                total += w * self.iou_gain * li
+                iou_terms[b] = torch.tensor([iou_sum / max(1, n_pos), n_pos], dtype=torch.float32)
+                if kept is not None:
+                    kept[3][b] = iou_map
+            gcls[b] = torch.from_numpy(gc * w).to(gcls.dtype).reshape(4, H, W)
+            greg[b] = torch.from_numpy(gr).to(greg.dtype).reshape(14, H, W)
+            terms[b] = torch.tensor([lc, lr, n_pos], dtype=torch.float32)
         if kept is not None:
             self.last_samples = tuple(torch.from_numpy(v) for v in kept)
         loss[0] = total

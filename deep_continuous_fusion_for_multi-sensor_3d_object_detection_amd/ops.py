@@ -1276,3 +1276,26 @@ def loss_anchor(cls, reg, anchors, boxes, target, counts, alpha, gamma, eps, gai
            _chk(target, "target"), _chk(counts, "counts"), B, Hh, W, float(alpha), float(gamma), float(eps), float(gain), int(reduction), loss,
            gcls, gcls.stride(0), greg, greg.stride(0), terms, ws, H.stream_ptr())
     return loss
+
+
+# ------------------------------------------------------------------ rotated-IoU regression term (iou_loss_gain)
+def loss_anchor_iou_workspace(B, Hh, W, device, iou_map=False):
+    """(workspace, iou_terms [B,2], iou_map fp64 [B,2,h*w] or None) of loss_anchor_iou for one map shape; the workspace's contents are
+    free between calls on one stream.  The map starts as zeros: rows of samples `loss_reduction: last` leaves out are never written."""
+    nbytes = H.lib().dcf_loss_anchor_iou_workspace_bytes(B, Hh, W)
+    if nbytes == 0:
+        raise H.DcfError("loss_anchor_iou: bad map shape %r" % ((B, Hh, W),))
+    return (torch.empty(nbytes // 8, dtype=torch.float64, device=device), torch.zeros((B, 2), dtype=torch.float32, device=device),
+            torch.zeros((B, 2, Hh * W), dtype=torch.float64, device=device) if iou_map else None)
+
+
+def loss_anchor_iou(reg, anchors, boxes, target, counts, kind, gain, reduction, loss, greg, iou_terms, ws, iou_map=None):
+    """The IoU regression term on per-anchor targets, after loss_anchor on the same stream: reg [B,14,h,w] fp32 view with unit cell stride,
+    anchors [2,7,h*w], boxes [B,max,>=7] fp32, target int32 [B,2,h*w] and counts int32 [B,4] on the device; kind 0 = 3-D, 1 = bird's-eye.
+    loss [1] and the seven greg elements of every positive anchor are ADDED to, iou_terms [B,2] = (mean IoU of the positives, N_b) and, if
+    given, iou_map fp64 [B,2,h*w] are written.  reduction: 0 last, 1 sum, 2 mean."""
+    B, _, Hh, W = reg.shape
+    H.call("dcf_loss_anchor_iou_fwd_bwd", reg, reg.stride(0), anchors, _chk(boxes, "boxes"), boxes.shape[1], boxes.shape[2], _chk(target, "target"),
+           _chk(counts, "counts"), B, Hh, W, int(kind), float(gain), int(reduction), loss, greg, greg.stride(0), _chk(iou_terms, "iou_terms"),
+           None if iou_map is None else _chk(iou_map, "iou_map"), ws, H.stream_ptr())
+    return loss

@@ -757,6 +757,13 @@ class Train(nn.Module):
         terms = self.loss_total.last_terms
         return None if terms is None else terms.clone()
 
+    def loss_iou(self):
+        """iou_loss_gain > 0 -- [B,2] fp32 = (mean rotated IoU of the positive anchors' decoded boxes with their labels, positive anchors)
+        per sample of the last step; zero rows for the samples `loss_reduction: last` leaves out (device tensor, a copy, no
+        synchronisation).  None when the term is off or nothing has been computed yet."""
+        iou = self.loss_total.last_iou
+        return None if iou is None else iou.clone()
+
     def skipped_steps(self):
         """Steps skipped for a non-finite gradient so far (device int64 tensor, a copy)."""
         return None if self.optimizer.amp is None else self.optimizer.amp.skipped_steps.clone()
@@ -1016,6 +1023,7 @@ def main():
             else:
                 print("epoch %d: learning rate %.6g, per parameter group %s" % (epoch, training.learning_rate(), " ".join("%.6g" % r for r in training.learning_rates())))
         terms_sum, terms_n = None, 0                                       # focal: the epoch's mean terms, added up on the device
+        iou_sum = None                                                     # iou_loss_gain: (sum of mean IoU x positives, positives), on the device
         pasted, pasted_frames = 0, 0                                       # augment_paste: accepted objects / frames of the epoch
         occluders, covering = 0, 0                                         # camera_mask.paste_occlusion: occluding patches / dropped objects
         for batch_ndx, batch in enumerate(loader):
@@ -1030,6 +1038,10 @@ def main():
                 counted = terms[-1:] if training.loss_total.reduction == "last" else terms
                 terms_sum = counted.mean(0) if terms_sum is None else terms_sum + counted.mean(0)
                 terms_n += 1
+            iou = training.loss_iou()
+            if iou is not None:                                            # weighted by the positives: the epoch mean is over anchors
+                step = torch.stack(((iou[:, 0] * iou[:, 1]).sum(), iou[:, 1].sum()))
+                iou_sum = step if iou_sum is None else iou_sum + step
             if batch_ndx % 100 == 0:
                 print("training at ", batch_ndx, "is processed, loss %.4f" % training.loss_value.item())
             if batch_ndx % 500 == 0 and batch_ndx != 0:                    # train.py:87-100
@@ -1053,6 +1065,9 @@ def main():
             cls_mean, reg_mean, npos_mean = (terms_sum / terms_n).tolist()
             what = "positive anchors" if training.loss_total.sampling == "anchor" else "positive cells"
             print("epoch %d: focal classification %.4f, regression %.4f, %s %.1f (batch means)" % (epoch, cls_mean, reg_mean, what, npos_mean))
+        if rank0 and iou_sum is not None:
+            total, n = iou_sum.tolist()
+            print("epoch %d: mean %s IoU of the positive anchors %.4f (%d anchors)" % (epoch, training.loss_total.iou_kind, total / max(n, 1.0), int(n)))
         _eval_barrier()
         if rank0:                                                          # train.py:105-122
             mean, cum, npos, nt, tp = evaluate(training, tester, test_dataset, test_loader, max_batches=int(config.get("eval_batches_epoch", 12)))   # `batch_ndx > 10`

@@ -801,6 +801,26 @@ int dcf_loss_anchor_fwd_bwd(const float *cls, int64_t cls_bstride, const float *
                             int W, float alpha, float gamma, float eps, float reg_gain, int reduction, float *loss, float *gcls,
                             int64_t gcls_bstride, float *greg, int64_t greg_bstride, float *terms, void *workspace, dcf_stream_t stream);
 
+/* (version 202 still: added without a new minor) Rotated-IoU regression term on the targets above (`iou_loss_gain`, DESIGN.md section
+ * 26; loss.anchor_iou_terms and loss.iou_value_grad are the host statements).  For every positive anchor j of a computed sample (target
+ * in [0, max_box)): q = label row target(j) (x, y, z, l, w, h, yaw; z at mid-height), p = the head's decode of the anchor's seven
+ * offsets r without the yaw wrap, in fp64 on the fp32 inputs: x = r0 diag + a0, y = r1 diag + a1, z = r2 a5 + a2, l = exp(r3) a3,
+ * w = exp(r4) a4, h = exp(r5) a5, yaw = r6 + a6, diag = sqrt(a3^2 + a4^2).  IoU = the 3-D IoU of dcf_eval_nms mode 2's geometry (kind 0)
+ * or its bird's-eye IoU (kind 1), computed by clipping the edges of each rectangle in the other, relative to q's centre.
+ *   L_b = sum_j (1 - IoU_j) / max(1, N_b), N_b = counts[b][0];   *loss += sum over the computed samples of wsample iou_gain L_b
+ *   (the workgroups' partial sums folded in a fixed order in double; *loss is read, so it must hold the value of dcf_loss_anchor_fwd_bwd,
+ *   launched before on the same stream);   greg[b][7a + c][i] += wsample iou_gain d L_b / d r_c for the positive anchors only -- one
+ *   lane owns a positive's seven elements, every other element of greg keeps its bits.  A disjoint pair adds 1 / max(1, N_b) to L_b and
+ *   seven zeros; a pair with a non-finite p or q gives NaN (value and its own seven gradients).  No atomics: one entry for deterministic
+ *   and plain runs.  iou_terms fp32 [B][2] = (sum_j IoU_j / max(1, N_b), N_b), zero rows for the samples reduction 0 leaves out.
+ *   iou_map fp64 [B][2][H*W] or NULL: IoU_j for a positive anchor, 0 for every other anchor of a computed sample.
+ *   workspace: dcf_loss_anchor_iou_workspace_bytes(B, H, W) bytes, 8-byte aligned, contents free on entry. */
+size_t dcf_loss_anchor_iou_workspace_bytes(int B, int H, int W);
+int dcf_loss_anchor_iou_fwd_bwd(const float *reg, int64_t reg_bstride, const float *anchors, const float *boxes, int max_box,
+                                int box_stride, const int32_t *target, const int32_t *counts, int B, int H, int W, int kind,
+                                float iou_gain, int reduction, float *loss, float *greg, int64_t greg_bstride, float *iou_terms,
+                                double *iou_map, void *workspace, dcf_stream_t stream);
+
 /* ------------------------------------------------- evaluation post-processing
  * What /root/reference/test.py:88-206 does on the host, box by box.
  * dcf_eval_score_filter: test.py:88-108.  pred [B][32][h][w] fp32 (the model output: scores in channels 2a+1, decoded boxes in
